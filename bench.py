@@ -10,7 +10,12 @@ the FASTA bytes already resident in HBM:
     regions) -> rg_pass (per bucket, by the next 9 bits) -> rg_finish (one
     LDS block per region: sort the rest, run-length uniq, compacted output)
 leaving the (k-mer, pos) rows device-resident.  ``value`` is that rate.
-Reported beside it:
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) sets up, warms up,
+times the N steps and prints the result line; ``--dump-outputs DIR`` also
+writes a fixed sample of the last step's rows as DIR/<name>.npy (see
+``dump_outputs``).  The roofline lines come from the HIP events of the timed
+steps themselves and are in every run; the other lines below take runs of
+their own and are reported only with ``--full``:
   * ``pinned_host``: the same step starting from pinned host bytes: chunked
     H2D copies on a copy stream overlapping the parse and the first region
     pass of the previous chunk (shard.StreamedPipeline), beside the serial
@@ -40,7 +45,8 @@ all-to-all of packed items over xGMI, per-bucket passes + LDS finish).  The
 rendezvous is RCCL only: rank 0 writes the RCCL id to a file, the barrier and
 the max-over-ranks time are RCCL collectives (no torch.distributed).
 ``--shard-gb 12.5`` gives the per-rank shape of BASELINE config 4
-(100 GB over 8 GPUs).
+(100 GB over 8 GPUs).  With ``--full`` an N > 1 run also times each line with
+overlapped rounds, adds the config-4 sub-line and the CPU baseline.
 """
 
 from __future__ import annotations
@@ -446,6 +452,53 @@ def extra_lines(args, dev, pipe, out, text, cfg2_path):
         out["file_to_file_config2"] = {"error": repr(e)}
 
 
+DUMP_SEED = 20210  # the row sample of --dump-outputs: fixed, so two builds dump the same rows
+DUMP_BLOCKS, DUMP_BLOCK_ROWS = 512, 2048  # 2^20 sampled rows: 32 MiB of float64 in all
+
+
+def dump_rows(n_out: int):
+    """Start rows of the sampled blocks (sorted, first and last block
+    included) and the block length; every row when there are few."""
+    import numpy as np
+
+    if n_out <= DUMP_BLOCKS * DUMP_BLOCK_ROWS:
+        return np.zeros(1 if n_out else 0, np.int64), n_out
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    last = n_out - DUMP_BLOCK_ROWS
+    starts = rng.integers(0, last + 1, size=DUMP_BLOCKS - 2, dtype=np.int64)
+    return np.sort(np.concatenate([[0, last], starts])).astype(np.int64), DUMP_BLOCK_ROWS
+
+
+def dump_outputs(dev, pipe, path: str) -> None:
+    """--dump-outputs: what the last timed step left for its caller, the
+    sorted (k-mer, pos | count) rows in out_keys / out_vals and their number,
+    as float64 .npy files in `path`.  Of more than 2^20 rows a fixed seeded
+    sample of blocks of consecutive rows is written (dump_rows), the same
+    rows in every run of the same arguments:
+      counts.npy  [n_kmers, n_out] of the step
+      rows.npy    row index of every sampled row
+      keys.npy    (rows, 2): high and low 32 bits of the 2k-bit key (exact)
+      vals.npy    uniq: the k-mer's position; count: its count"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    dev.sync()
+    vb = pipe.count_bytes if pipe.mode == "count" else pipe.pos_bytes
+    vt = np.uint32 if vb == 4 else np.uint64
+    starts, m = dump_rows(pipe.n_out)
+    keys = [dev.download(pipe.out_keys, m, np.uint64, 8 * int(s)) for s in starts]
+    vals = [dev.download(pipe.out_vals, m, vt, vb * int(s)) for s in starts]
+    keys = np.concatenate(keys) if keys else np.zeros(0, np.uint64)
+    vals = np.concatenate(vals) if vals else np.zeros(0, vt)
+    rows = (starts[:, None] + np.arange(m, dtype=np.int64)[None, :]).reshape(-1)
+    np.save(os.path.join(path, "counts.npy"), np.array([pipe.n_kmers, pipe.n_out], np.float64))
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "keys.npy"),
+            np.stack([keys >> np.uint64(32), keys & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64))
+    np.save(os.path.join(path, "vals.npy"), vals.astype(np.float64))
+    log("dumped %d of %d rows to %s" % (len(rows), pipe.n_out, path))
+
+
 def run_single(args):
     import numpy as np  # noqa: F401
     import inputs
@@ -490,7 +543,10 @@ def run_single(args):
         "roofline": dom, "sort_pass_roofline": sp, "cpu_baseline": None,
     }
     pipe.timing(False)
-    if not args.quick:
+    if args.dump_outputs:
+        dump_outputs(dev, pipe, args.dump_outputs)
+    extras = args.full and not args.quick
+    if extras:
         try:
             out["output"] = output_lines(dev, pipe, args.k, args.mode)
             d2h = d2h_probe(dev)
@@ -500,7 +556,7 @@ def run_single(args):
             out["output"] = {"error": repr(e)}
     pipe.free()
     cfg2_path = None
-    if not args.quick:
+    if extras:
         try:
             # config 2's FASTA as a file, for the end-to-end CLI line below
             # (never fatal to the GPU number: any failure is reported in the
@@ -517,7 +573,7 @@ def run_single(args):
                     os.remove(cfg2_path)
                 except OSError:
                     pass
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args.k, args.mode)
         except Exception as e:  # reported, never fatal to the GPU number
@@ -642,16 +698,16 @@ def run_dist(args, world: int, rank: int, local: int):
     canon = args.canonical
     if canon and args.mode != "count":
         raise SystemExit("--canonical counts (config 5): use --mode count")
-    # N > 1: each line also timed with overlapped rounds (opt-in in the
-    # product until an N > 1 run shows which is faster)
-    ov = world > 1 and not canon
+    # N > 1 with --full: each line also timed with overlapped rounds (opt-in
+    # in the product until an N > 1 run shows which is faster)
+    ov = args.full and world > 1 and not canon
     ln = dist_line(args, dev, world, rank, per, args.mode, canon, reparse, args.steps, args.warmup, "bench",
                    also_overlap=ov)
     # BASELINE config 4 (100 GB synthetic FASTA, k=21, N GPUs): after the
     # weak-scaling line, the same job at 100 / N GB per rank, count mode,
-    # parsed at setup -- so the driver's plain `--gpus N` run measures it too
+    # parsed at setup -- so one `--gpus N --full` run measures it too
     sub = None
-    if world > 1 and args.config4 and args.shard_gb is None and not canon:
+    if args.full and world > 1 and args.config4 and args.shard_gb is None and not canon:
         per4 = int(100e9 / world)
         sub = dist_line(args, dev, world, rank, per4, "count", False, False, args.config4_steps, 1, "bench4",
                         also_overlap=ov)
@@ -699,7 +755,7 @@ def run_dist(args, world: int, rank: int, local: int):
                                            "byte-range shards, key rounds + RCCL all-to-all" % (world, 100.0 / world))
         # the C port on the host's cores, after every rank has left the GPU
         # work (the other ranks exit; the GPUs are idle while it runs)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.k, args.mode)
             except Exception as e:  # reported, never fatal to the GPU number
@@ -800,8 +856,16 @@ def parse_args(argv=None):
     ap.add_argument("--shard-gb", type=float, default=None, help="FASTA GB per rank on the multi-GPU path "
                                                                  "(12.5 = BASELINE config 4's shape)")
     ap.add_argument("--chunk-mb", type=int, default=128, help="chunk size of the pinned-host line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="HBM-resident line only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line, also every line that takes runs of its own: the CPU baseline, the "
+                         "pinned-host, output and file-to-file lines; N > 1: overlapped rounds and the config-4 "
+                         "sub-line.  Off by default: a plain run times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single-GPU path: after the timed steps write the last step's rows (a fixed seeded sample "
+                         "of them) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--quick", action="store_true",
+                    help="with --full: HBM-resident line (and the CPU baseline) only (profiling runs)")
     ap.add_argument("--path", choices=["region", "split", "full"], default="region",
                     help="single-GPU engine path (region falls back to split outside its domain)")
     ap.add_argument("--dist", action="store_true", help="run the multi-GPU pipeline even at world size 1")
@@ -827,6 +891,9 @@ def main() -> None:
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and (args.gpus > 1 or args.dist or args.canonical):
+        raise SystemExit("--dump-outputs writes the single-GPU step's rows: not with --gpus N > 1, --dist or "
+                         "--canonical")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dist or args.canonical):
         # no launcher: start the ranks here (this process never touches the GPU)
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))

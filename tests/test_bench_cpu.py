@@ -12,6 +12,8 @@ import subprocess
 import sys
 import time
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -159,7 +161,7 @@ class _Dev:
 
 
 def test_multi_gpu_line_carries_config4_and_rccl_ranks(monkeypatch, capsys):
-    """`bench.py --gpus N` (N > 1, the driver's plain run): after the
+    """`bench.py --gpus N --full` (N > 1): after the
     1 GB-per-rank weak-scaling line, a config4 sub-line of BASELINE config 4
     (100 GB over N ranks: 100/N GB per rank, count, parsed at setup), each with
     the RCCL communicator's own rank count."""
@@ -168,7 +170,7 @@ def test_multi_gpu_line_carries_config4_and_rccl_ranks(monkeypatch, capsys):
     calls = []
     monkeypatch.setattr(bench, "dist_line", _fake_line(calls))
     monkeypatch.setattr(engine, "Device", _Dev)
-    args = bench.parse_args(["--gpus", "8", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"])
+    args = bench.parse_args(["--gpus", "8", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"])
     bench.run_dist(args, 8, 0, 0)
     out = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert out["n_gpus"] == 8 and out["config"]["rccl_ranks"] == 8 and out["steps"] == 4
@@ -192,9 +194,46 @@ def test_multi_gpu_line_carries_config4_and_rccl_ranks(monkeypatch, capsys):
     for argv, world in ((["--gpus", "2", "--no-config4"], 2), (["--gpus", "2", "--shard-gb", "12.5"], 2),
                         (["--dist"], 1)):
         calls.clear()
-        bench.run_dist(bench.parse_args(argv + ["--no-cpu-baseline"]), world, 0, 0)
+        bench.run_dist(bench.parse_args(argv + ["--full", "--no-cpu-baseline"]), world, 0, 0)
         out = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
         assert len(calls) == 1 and "config4" not in out and out["config"]["rccl_ranks"] == world
         assert calls[0]["also_overlap"] == (world > 1)
         if world == 1:
             assert "at one rank the whole exchange is that copy" in out["config"]["workload"]
+
+
+def test_plain_multi_gpu_run_times_the_main_line_only(monkeypatch, capsys):
+    """Without --full an N > 1 run is the weak-scaling line alone: no
+    overlapped steps, no config4 sub-line, no CPU baseline."""
+    from kman_amd import engine
+
+    calls = []
+    monkeypatch.setattr(bench, "dist_line", _fake_line(calls))
+    monkeypatch.setattr(engine, "Device", _Dev)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("CPU baseline in a plain run"))
+    bench.run_dist(bench.parse_args(["--gpus", "8", "--steps", "4", "--warmup", "1"]), 8, 0, 0)
+    out = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert [(c["tag"], c["also_overlap"], c["steps"]) for c in calls] == [("bench", False, 4)]
+    assert "config4" not in out and out["cpu_baseline"] is None and out["config"]["overlapped"] is None
+    assert out["steps"] == 4 and out["ms_per_step"] == 10.0 and out["n_gpus"] == 8
+
+
+def test_dump_rows_are_fixed_and_in_range():
+    """--dump-outputs samples the same blocks of rows in every run, the first
+    and the last row among them, none past the end; few rows are all kept."""
+    n = 999_772_781
+    a, m = bench.dump_rows(n)
+    b, _ = bench.dump_rows(n)
+    assert (a == b).all() and m == bench.DUMP_BLOCK_ROWS and len(a) == bench.DUMP_BLOCKS
+    assert a[0] == 0 and a[-1] + m == n and (a >= 0).all() and (a[1:] >= a[:-1]).all()
+    assert 8 * 4 * len(a) * m <= 64 << 20  # counts, rows, keys (2 columns), vals as float64
+    s, m = bench.dump_rows(5000)
+    assert list(s) == [0] and m == 5000
+    s, m = bench.dump_rows(0)
+    assert len(s) == 0 and m == 0
+
+
+def test_dump_outputs_needs_the_single_gpu_path():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", "x"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and r.stdout.strip() == ""
