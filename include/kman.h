@@ -9,6 +9,7 @@
  *
  *   kman_parse_fasta   SmartFastaParser.parse            kmermaid/parsers.py:86-128
  *                      + record name rule                 kmermaid/batcher.py:551
+ *   kman_parse_fastq   the same outputs from four-line FASTQ (not in the reference)
  *   kman_extract       Sequence.yield_kmers / kmerator    kmermaid/seq.py:285-359
  *                      + alphabet check / mkrc            kmermaid/seq.py:279,318,500-509
  *   kman_sort          Batch.sorted (stable, by .seq)     kmermaid/batch.py:156-168
@@ -139,7 +140,7 @@ int kman_copy_d2h_wait(kman_ctx *ctx, int slot);
 /* ------------------------------------------------------------------- timing
  * Optional per-kernel timing with HIP events recorded on the context's own
  * stream around every launch (bench.py's live roofline).  Tags: "parse",
- * "extract", "sort_hist", "sort_pass", "rle_count", "rle_uniq".
+ * "parse_fastq", "extract", "sort_hist", "sort_pass", "rle_count", "rle_uniq".
  * kman_timing_query synchronises and returns launches and summed ms. */
 int kman_timing_enable(kman_ctx *ctx, int enable);
 int kman_timing_query(kman_ctx *ctx, const char *tag, uint64_t *launches, double *total_ms);
@@ -171,6 +172,22 @@ int kman_parse_fasta(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uin
 int kman_parse_fasta_at(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint32_t flags, uint8_t *d_codes,
                         uint64_t code_off, uint64_t *d_rec_hdr, uint64_t *d_rec_seq, uint64_t rec_cap,
                         kman_parse_info *info);
+
+/* Strict four-line FASTQ text -> the same outputs, with the argument meanings,
+ * capacities, alignment requirements and error conventions of
+ * kman_parse_fasta (not in the reference, which reads FASTA only).  Lines are
+ * split as for FASTA ("\n", "\r\n", a lone "\r"); trailing empty lines are
+ * dropped and the rest padded with empty lines to a multiple of four.  Of
+ * every four lines the first starts with '@' (d_rec_hdr[r] = its byte
+ * offset), the second is the sequence, cleaned as a FASTA sequence line
+ * (right-stripped, ' ' and '\r' removed; a leading '>' is an invalid base),
+ * the third starts with '+', the fourth (quality, never in d_codes) has as
+ * many bytes before its terminator as the second.  Wrapped FASTQ is not
+ * supported.  KMAN_EFORMAT: no lines ("premature end of file or empty file"),
+ * or "FASTQ record <1-based>: <rule>" for the first record that breaks one;
+ * info is zeroed then.  Launches are timed under the tag "parse_fastq". */
+int kman_parse_fastq(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_codes,
+                     uint64_t *d_rec_hdr, uint64_t *d_rec_seq, uint64_t rec_cap, kman_parse_info *info);
 
 /* Number of k-mers kman_extract will emit (valid windows x (RC ? 2 : 1)). */
 int kman_count_kmers(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases, uint32_t k,

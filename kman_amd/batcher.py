@@ -150,8 +150,11 @@ class FastaBatcher(BatcherThreading):
     def __init__(self, scan_mode: "FastaBatcher.MODE" = MODE.KMERS, reverse: bool = False, threads: int = 1,
                  size: int = BatcherThreading.DEFAULT_BATCH_SIZE, natype: NATYPES = BatcherThreading.DEFAULT_NATYPE,
                  tmp: Optional[str] = None, device: Optional[engine.Device] = None,
-                 distributed: Optional[bool] = None):
+                 distributed: Optional[bool] = None, fmt: str = "auto"):
         super().__init__(size, threads, natype, tmp if tmp is not None else tempfile.gettempdir())
+        if fmt not in engine.FORMATS:
+            raise AssertionError("format must be one of %s, got %r" % (", ".join(engine.FORMATS), fmt))
+        self.fmt = fmt  # input format: "auto" (engine.sniff_format), "fasta" or "fastq"
         self.mode = scan_mode
         self.doReverseComplement = reverse
         self._device = device
@@ -194,7 +197,8 @@ class FastaBatcher(BatcherThreading):
 
         dev = self._device or engine.default_device()
         dist = launch.distributed() if self._distributed is None else self._distributed
-        if dist and k <= engine.MAX_K:
+        fmt = engine.sniff_file(fasta) if self.fmt == "auto" else self.fmt
+        if dist and k <= engine.MAX_K and fmt != "fastq":  # (the byte-range shards cut FASTA only)
             # this rank's byte range only; ONE batch of its windows, joined
             # across the ranks by KJoiner.join (the batch cut does not change
             # count / uniq output)
@@ -203,10 +207,13 @@ class FastaBatcher(BatcherThreading):
             n = src.n_kmers
             self.feed_collection([Batch.from_source(src, 0, n, max(1, n), self.tmp)], feedMode)
             return self
-        src = FastaSource(dev, None, k, self.doReverseComplement, path=fasta)
+        src = FastaSource(dev, None, k, self.doReverseComplement, path=fasta, fmt=fmt)
         self.source = src
-        for name in src.parsed.names:
-            logging.info("Batching record '%s'..." % name.decode("utf-8", "surrogateescape"))
+        if fmt == "fastq":  # (reads: millions of records, one line for all)
+            logging.info("Batching %d reads..." % src.parsed.n_records)
+        else:
+            for name in src.parsed.names:
+                logging.info("Batching record '%s'..." % name.decode("utf-8", "surrogateescape"))
         batches = []
         if self.mode == self.MODE.KMERS:
             n = src.n_kmers

@@ -10,6 +10,7 @@ The mapping to the reference (kmermaid 1.0.0):
 engine function        reference                                   kernel(s)
 =====================  ==========================================  ============================
 ``parse``              SmartFastaParser.parse, parsers.py:86-128   parse_reduce/scan/emit
+``parse_fastq``        (four-line FASTQ; not in the reference)     fq_reduce/scan/emit/validate
 ``record names``       record[0].split(" ")[0], batcher.py:551     host (names only)
 ``extract``            Sequence.yield_kmers, seq.py:285-328        extract_kernel
 ``sort``               Batch.sorted, batch.py:156-168              onesweep_pass x P
@@ -23,6 +24,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections.abc import Sequence as _SequenceABC
 from ctypes import byref, c_int, c_size_t, c_uint32, c_uint64, c_void_p
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -203,8 +205,198 @@ class Parsed:
         self.codes.free()
 
 
-def parse(dev: Device, text: bytes) -> Parsed:
-    """FASTA bytes -> device codes + record table (kman_parse_fasta)."""
+FORMATS = ("auto", "fasta", "fastq")
+
+
+def sniff_format(head: bytes) -> str:
+    """``"fastq"`` if and only if the first byte of the first non-empty line
+    of `head` (the beginning of an input) is ``@``; everything else is
+    ``"fasta"``, so every input that parses as FASTA keeps doing so."""
+    s = bytes(head).lstrip(b"\r\n")
+    return "fastq" if s[:1] == b"@" else "fasta"
+
+
+def _resolve_format(fmt: str, head) -> str:
+    """`fmt` checked; ``auto`` decided from the input's head (`head`: bytes,
+    or a callable ``offset -> bytes`` that reads the input piecewise)."""
+    if fmt not in FORMATS:
+        raise AssertionError("format must be one of %s, got %r" % (", ".join(FORMATS), fmt))
+    if fmt != "auto":
+        return fmt
+    if not callable(head):
+        return sniff_format(head)
+    at = 0
+    while True:  # (more than one piece only when the input starts with 64 KiB of blank lines)
+        piece = head(at)
+        if not piece or piece.strip(b"\r\n"):
+            return sniff_format(piece)
+        at += len(piece)
+
+
+def sniff_file(path: str) -> str:
+    """sniff_format of a file's head (a ``.gz`` is inflated only that far)."""
+    if path.endswith(".gz"):
+        import gzip
+
+        with gzip.open(path, "rb") as fh:
+            return _resolve_format("auto", lambda at: fh.read(1 << 16))
+    with open(path, "rb") as fh:
+        return _resolve_format("auto", lambda at: fh.read(1 << 16))
+
+
+class BlobNames(_SequenceABC):
+    """The record names as a read-only sequence over ``names_blob`` /
+    ``name_off`` (no per-record objects until one is asked for)."""
+
+    def __init__(self, blob: bytes, off: np.ndarray):
+        self._blob, self._off = blob, off
+
+    def __len__(self) -> int:
+        return len(self._off) - 1
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return self._blob[int(self._off[i]):int(self._off[i + 1])]
+
+    def __iter__(self):
+        b, o = self._blob, self._off.tolist()
+        return (b[o[i]:o[i + 1]] for i in range(len(o) - 1))
+
+    def __eq__(self, other):
+        try:
+            return len(self) == len(other) and all(a == b for a, b in zip(self, other))
+        except TypeError:
+            return NotImplemented
+
+    __hash__ = None
+
+    def __repr__(self) -> str:
+        return "BlobNames(%d names)" % len(self)
+
+
+_NAME_ROWS = 1 << 16  # header lines gathered per numpy block
+
+
+def fastq_names(text, rec_hdr: np.ndarray) -> Tuple[bytes, np.ndarray]:
+    """``(names_blob, name_off)`` of the records whose ``@`` sit at `rec_hdr`
+    in `text`: ``_title_name`` of every header line, computed with numpy over
+    blocks of header lines.  A line of plain ASCII without the whitespace that
+    ``str.rstrip`` treats unlike ``" "`` (``\\t \\v \\f \\x1c-\\x1f``) has its
+    name end at its first space or at its end; only the other lines go through
+    ``_title_name`` itself."""
+    R = len(rec_hdr)
+    n = len(text)
+    t = np.frombuffer(text, dtype=np.uint8)
+    lens = np.zeros(R, dtype=np.int64)
+    pieces: List[bytes] = []
+    try:
+        for r0 in range(0, R, _NAME_ROWS):
+            start = rec_hdr[r0:r0 + _NAME_ROWS].astype(np.int64) + 1
+            m = len(start)
+            nlen = np.zeros(m, dtype=np.int64)
+            odd = np.zeros(m, dtype=bool)
+            todo = np.arange(m)
+            base, W = np.zeros(m, dtype=np.int64), 64
+            # the window [base, base + W) of every unfinished line, W doubling
+            # for the lines that did not end in it
+            while len(todo):
+                idx = (start[todo] + base[todo])[:, None] + np.arange(W)[None, :]
+                past = idx >= n
+                c = t[np.minimum(idx, n - 1)]
+                stop = (c == 0x0A) | (c == 0x0D) | past
+                bad = ((c >= 0x80) | (c == 9) | (c == 11) | (c == 12) | ((c >= 0x1C) & (c <= 0x1F))) & ~stop
+                has_stop = stop.any(axis=1)
+                first_stop = np.where(has_stop, stop.argmax(axis=1), W)
+                inline = np.arange(W)[None, :] < first_stop[:, None]
+                odd[todo] |= (bad & inline).any(axis=1)
+                space = (c == 0x20) & inline
+                has_sp = space.any(axis=1)
+                first_sp = np.where(has_sp, space.argmax(axis=1), W)
+                # name bytes in this window: up to the first space / the line's end
+                grow = nlen[todo] == base[todo]  # (no space met in the earlier windows)
+                take = np.where(grow, np.minimum(first_sp, first_stop), 0)
+                nlen[todo] += take
+                base[todo] += W
+                todo = todo[~has_stop]
+                W *= 2
+            nlen[odd] = 0
+            sel = np.repeat(start, nlen) + (np.arange(int(nlen.sum())) - np.repeat(np.cumsum(nlen) - nlen, nlen))
+            blob = t[sel].tobytes()
+            if odd.any():
+                offs = np.concatenate([[0], np.cumsum(nlen)])
+                prev = 0
+                for j in np.nonzero(odd)[0].tolist():
+                    nm = _title_name(text, int(start[j]) - 1)
+                    pieces.append(blob[prev:int(offs[j])])
+                    pieces.append(nm)
+                    prev = int(offs[j])
+                    nlen[j] = len(nm)
+                pieces.append(blob[prev:])
+            else:
+                pieces.append(blob)
+            lens[r0:r0 + m] = nlen
+    finally:
+        del t  # (releases an mmap's buffer)
+    name_off = np.zeros(R + 1, dtype=np.uint64)
+    if R:
+        name_off[1:] = np.cumsum(lens, dtype=np.uint64)
+    return b"".join(pieces), name_off
+
+
+def _parsed_fastq(dev: Device, codes: DeviceBuffer, info, rec_hdr, rec_seq, text) -> Parsed:
+    blob, name_off = fastq_names(text, rec_hdr)
+    return Parsed(dev, codes, int(info.n_bases), int(info.n_records), rec_hdr, rec_seq, BlobNames(blob, name_off),
+                  blob, name_off)
+
+
+def parse_fastq(dev: Device, text: bytes) -> Parsed:
+    """Four-line FASTQ bytes -> device codes + record table (kman_parse_fastq):
+    the same ``Parsed`` as ``parse`` gives for the FASTA of the same records;
+    the names follow the record name rule applied to the ``@`` line."""
+    n = len(text)
+    if n == 0:
+        raise AssertionError("premature end of file or empty file")
+    L = N.lib()
+    d_text = dev.alloc(n + 64)
+    codes = dev.alloc(n + 64)
+    try:
+        dev.upload(d_text, text)
+        phases.mark("h2d")
+        # record capacity: four lines of at least one byte each, but for the last record
+        cap = n // 4 + 1
+        d_hdr = dev.alloc(8 * cap)
+        d_seq = dev.alloc(8 * cap)
+        try:
+            info = N.ParseInfo()
+            rc = L.kman_parse_fastq(dev.ctx, c_void_p(d_text.ptr), n, c_void_p(codes.ptr), c_void_p(d_hdr.ptr),
+                                    c_void_p(d_seq.ptr), cap, byref(info))
+            N.check(dev.ctx, rc, "kman_parse_fastq")
+            R = int(info.n_records)
+            rec_hdr = dev.download(d_hdr, R, np.uint64)
+            rec_seq = dev.download(d_seq, R, np.uint64)
+        finally:
+            d_hdr.free()
+            d_seq.free()
+    except BaseException:
+        codes.free()
+        raise
+    finally:
+        d_text.free()
+    p = _parsed_fastq(dev, codes, info, rec_hdr, rec_seq, text)
+    phases.mark("parse")
+    return p
+
+
+def parse(dev: Device, text: bytes, fmt: str = "auto") -> Parsed:
+    """FASTA bytes -> device codes + record table (kman_parse_fasta); FASTQ
+    bytes (`fmt`, ``auto``: sniff_format) go to parse_fastq."""
+    if _resolve_format(fmt, lambda at: bytes(text[at:at + (1 << 16)])) == "fastq":
+        return parse_fastq(dev, text)
     n = len(text)
     if n == 0:
         raise AssertionError("premature end of file or empty file")
@@ -237,15 +429,16 @@ def parse(dev: Device, text: bytes) -> Parsed:
     return Parsed(dev, codes, int(info.n_bases), R, rec_hdr, rec_seq, names, b"".join(names), name_off)
 
 
-def parse_file(dev: Device, path: str) -> Parsed:
-    """kman_parse_fasta of a FASTA file (batcher.py:480 reads it whole).  A
+def parse_file(dev: Device, path: str, fmt: str = "auto") -> Parsed:
+    """kman_parse_fasta of a FASTA file (batcher.py:480 reads it whole), or
+    kman_parse_fastq of a FASTQ file (`fmt`, ``auto``: sniff_format).  A
     plain file is read in _FMT_SLICE chunks straight into two pinned stages,
     each chunk's H2D (on the copy stream) running while the next chunk is
     read, so the text crosses host memory once and no pageable copy is made;
     the record names come from the file's header lines (mmap).  Gzip input
     is inflated into memory and parsed from there (read_input + parse)."""
     if path.endswith(".gz"):
-        return parse(dev, read_input(path))
+        return parse(dev, read_input(path), fmt)
     import mmap
 
     L = N.lib()
@@ -253,6 +446,7 @@ def parse_file(dev: Device, path: str) -> Parsed:
         n = os.fstat(fh.fileno()).st_size
         if n == 0:
             raise AssertionError("premature end of file or empty file")
+        fq = _resolve_format(fmt, lambda at: os.pread(fh.fileno(), 1 << 16, at)) == "fastq"
         d_text = dev.alloc(n + 64)
         codes = dev.alloc(n + 64)
         try:
@@ -276,14 +470,14 @@ def parse_file(dev: Device, path: str) -> Parsed:
                 i += 1
             N.check(dev.ctx, L.kman_copy_sync(dev.ctx), "kman_copy_sync")
             phases.mark("file_read+h2d")
-            cap = n // 2 + 1
+            cap = n // 4 + 1 if fq else n // 2 + 1
             d_hdr = dev.alloc(8 * cap)
             d_seq = dev.alloc(8 * cap)
             try:
                 info = N.ParseInfo()
-                N.check(dev.ctx, L.kman_parse_fasta(dev.ctx, c_void_p(d_text.ptr), n, c_void_p(codes.ptr),
-                                                    c_void_p(d_hdr.ptr), c_void_p(d_seq.ptr), cap, byref(info)),
-                        "kman_parse_fasta")
+                fn, what = (L.kman_parse_fastq, "kman_parse_fastq") if fq else (L.kman_parse_fasta, "kman_parse_fasta")
+                N.check(dev.ctx, fn(dev.ctx, c_void_p(d_text.ptr), n, c_void_p(codes.ptr), c_void_p(d_hdr.ptr),
+                                    c_void_p(d_seq.ptr), cap, byref(info)), what)
                 R = int(info.n_records)
                 rec_hdr = dev.download(d_hdr, R, np.uint64)
                 rec_seq = dev.download(d_seq, R, np.uint64)
@@ -297,6 +491,14 @@ def parse_file(dev: Device, path: str) -> Parsed:
             d_text.free()
         mm = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
         try:
+            if fq:
+                try:
+                    p = _parsed_fastq(dev, codes, info, rec_hdr, rec_seq, mm)
+                except BaseException:
+                    codes.free()
+                    raise
+                phases.mark("parse")
+                return p
             names = [_title_name(mm, int(h)) for h in rec_hdr]
         finally:
             mm.close()
@@ -312,9 +514,7 @@ def check_empty_names(p: Parsed, k: int) -> None:
     ``SequenceCoords.from_str`` (seq.py:106-127, via batch.py:170-186) whose
     regex needs a non-empty record name: a record with an empty name that
     yields any k-mer raises AssertionError before any output is written."""
-    for r, nm in enumerate(p.names):
-        if nm:
-            continue
+    for r in np.nonzero(np.diff(p.name_off) == 0)[0].tolist():  # (the records with an empty name)
         b = int(p.rec_seq[r])
         e = int(p.rec_seq[r + 1]) if r + 1 < p.n_records else p.n_bases
         if e - b < k:
@@ -1153,13 +1353,13 @@ def count_groups(p: Parsed, k: int, rc: bool = False, canonical: bool = False, o
 
 
 def abundance_hist(text: bytes, k: int, canonical: bool = True, nbins: int = 10001,
-                   dev: Optional[Device] = None) -> np.ndarray:
+                   dev: Optional[Device] = None, fmt: str = "auto") -> np.ndarray:
     """k-mer abundance spectrum (BASELINE config 5; SURVEY §8f-1, not in the
     reference): h[c] = distinct (canonical) k-mers seen c times, h[-1] every
     count >= nbins - 1 (kman_count_hist over the count output)."""
     dev = dev or default_device()
     _check_k(k, wide=True)
-    p = parse(dev, text)
+    p = parse(dev, text, fmt)
     try:
         r = count_groups(p, k, False, canonical, ordered=False)
         d_h = dev.alloc(8 * nbins)

@@ -79,5 +79,12 @@ def compress():
     return click.option("--compress", "-C", is_flag=True, help="Compress output files.")
 
 
+def input_format():
+    return click.option("--format", "-f", "input_format", type=click.Choice(["auto", "fasta", "fastq"],
+                                                                          case_sensitive=True),
+                        default="auto", help="INPUT format; auto: fastq if the first non-empty line starts "
+                                             "with '@', else fasta. Default: auto")
+
+
 def re_sort():
     return click.option("--re-sort", "-R", is_flag=True, help="Force batch re-sorting, when loaded with -B.")

@@ -35,10 +35,10 @@ def main():
     """Entry point."""
 
 
-def _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist=False):
+def _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist=False, fmt="auto"):
     return (
         FastaBatcher(scan_mode=FastaBatcher.MODE[scan_mode], reverse=reverse, size=batch_size, threads=threads,
-                     tmp=tmp, distributed=dist)
+                     tmp=tmp, distributed=dist, fmt=fmt)
         .do(input_path, k, BatcherThreading.FEED_MODE[batch_mode])
         .collection
     )
@@ -53,8 +53,9 @@ Counting modes:
        VEC_COUNT / VEC_COUNT_MASKED: abundance vectors; like the reference,
                  they raise NotImplementedError, unless KMAN_VEC_COUNT=1
                  selects this engine's vector writer (INTEGRATION.md §4)
-The INPUT file can be gzipped.  Launched one process per GPU (WORLD_SIZE >
-1), the join runs across the GPUs into one OUTPUT.
+INPUT fasta or fastq file, plain or gzipped.  Launched one process per GPU
+(WORLD_SIZE > 1), the join runs across the GPUs into one OUTPUT (a fastq
+INPUT runs on rank 0 alone).
 """)
 @args.input_path()
 @args.output_path(file_okay=True)
@@ -69,31 +70,44 @@ The INPUT file can be gzipped.  Launched one process per GPU (WORLD_SIZE >
 @args.threads()
 @args.tmp()
 @args.re_sort()
+@args.input_format()
 def count(input_path: str, output_path: str, k: int, reverse: bool = False, scan_mode: str = "KMERS",
           batch_size: int = 1000000, batch_mode: str = "APPEND", previous_batches: Optional[str] = None,
           count_mode: str = "SEQ_COUNT", memory_mode: str = "NORMAL", threads: int = 1,
-          tmp: str = tempfile.gettempdir(), re_sort: bool = False) -> None:
+          tmp: str = tempfile.gettempdir(), re_sort: bool = False, input_format: str = "auto") -> None:
     input_file_exists(input_path)
     set_tempdir(tmp)
-    dist = _multi_gpu(k, previous_batches, count_mode)
+    dist = _multi_gpu(k, previous_batches, count_mode, input_path, input_format)
     if dist is None:
         return  # (a rank other than 0, for work outside the multi-GPU domain)
     if previous_batches is not None:
         batches = load_batches(previous_batches, threads, re_sort)
     else:
-        batches = _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist)
+        batches = _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist,
+                           input_format)
     prep_joiner(KJoinerThreading(KJoiner.MODE[count_mode], KJoiner.MEMORY[memory_mode]), len(batches),
                 threads).join(batches, output_path)
     logging.info("That's all!")
 
 
-def _multi_gpu(k: int, previous_batches: Optional[str], count_mode: str = "SEQ_COUNT") -> Optional[bool]:
+def _is_fastq(input_path: Optional[str], input_format: str) -> bool:
+    """The input's format as every rank decides it alone, from the file's head."""
+    if input_format != "auto":
+        return input_format == "fastq"
+    return input_path is not None and engine.sniff_file(input_path) == "fastq"
+
+
+def _multi_gpu(k: int, previous_batches: Optional[str], count_mode: str = "SEQ_COUNT",
+               input_path: Optional[str] = None, input_format: str = "auto") -> Optional[bool]:
     """Under a one-process-per-GPU launch (kman_amd/launch.py): True = this
     rank joins across the GPUs; False = the single-GPU path (no launch, or
     rank 0 alone for work outside the multi-GPU domain: k > 32, -B reloads,
-    VEC_* modes); None = a rank that leaves that work to rank 0."""
+    VEC_* modes, fastq input); None = a rank that leaves that work to rank 0."""
     if not launch.distributed():
         return False
+    if k > 1 and previous_batches is None and _is_fastq(input_path, input_format):
+        launch.log_solo("fastq input")  # (the byte-range shards cut FASTA only)
+        return False if launch.solo_rank() else None
     if k <= 1 or (k <= engine.MAX_K and previous_batches is None and count_mode in ("SEQ_COUNT", "UNIQUE")):
         return True  # (k <= 1 raises in FastaBatcher.do on every rank, as the reference)
     launch.log_solo("k=%d%s%s" % (k, " -B" if previous_batches else "", "" if count_mode == "SEQ_COUNT"
@@ -115,7 +129,7 @@ def prep_joiner(joiner: KJoinerThreading, n_batches: int, threads: int = 1) -> K
 
 
 @main.command(name="uniq", context_settings=CONTEXT_SETTINGS,
-              help="Extract all k-mers that appear only once in the INPUT fasta file.")
+              help="Extract all k-mers that appear only once in the INPUT fasta or fastq file, plain or gzipped.")
 @args.input_path()
 @args.output_path(file_okay=True)
 @args.k()
@@ -127,18 +141,21 @@ def prep_joiner(joiner: KJoinerThreading, n_batches: int, threads: int = 1) -> K
 @args.threads()
 @args.tmp()
 @args.re_sort()
+@args.input_format()
 def uniq(input_path: str, output_path: str, k: int, reverse: bool = False, scan_mode: str = "KMERS",
          batch_size: int = 1000000, batch_mode: str = "APPEND", previous_batches: Optional[str] = None,
-         threads: int = 1, tmp: str = tempfile.gettempdir(), re_sort: bool = False) -> None:
+         threads: int = 1, tmp: str = tempfile.gettempdir(), re_sort: bool = False,
+         input_format: str = "auto") -> None:
     input_file_exists(input_path)
     set_tempdir(tmp)
-    dist = _multi_gpu(k, previous_batches, "UNIQUE")
+    dist = _multi_gpu(k, previous_batches, "UNIQUE", input_path, input_format)
     if dist is None:
         return
     if previous_batches is not None:
         batches = load_batches(previous_batches, threads, re_sort)
     else:
-        batches = _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist)
+        batches = _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist,
+                           input_format)
     joiner = KJoinerThreading()
     joiner.threads = threads
     joiner.batch_size = max(2, int(len(batches) / max(1, threads)))
@@ -147,10 +164,9 @@ def uniq(input_path: str, output_path: str, k: int, reverse: bool = False, scan_
 
 
 @main.command(name="batch", context_settings=CONTEXT_SETTINGS, help="""
-Generate batches of k-mers from an INPUT fasta file.
+Generate batches of k-mers from an INPUT fasta or fastq file, plain or gzipped.
 
 Batches are written to an OUTPUT folder, which must be empty or non-existent.
-The INPUT file can be gzipped.
 """)
 @args.input_path()
 @args.output_path(dir_okay=True)
@@ -162,9 +178,10 @@ The INPUT file can be gzipped.
 @args.threads()
 @args.tmp()
 @args.compress()
+@args.input_format()
 def batch(input_path: str, output_path: str, k: int, reverse: bool = False, scan_mode: str = "KMERS",
           batch_size: int = 1000000, batch_mode: str = "APPEND", threads: int = 1,
-          tmp: str = tempfile.gettempdir(), compress: bool = False) -> None:
+          tmp: str = tempfile.gettempdir(), compress: bool = False, input_format: str = "auto") -> None:
     input_file_exists(input_path)
     if launch.distributed() and not launch.solo_rank():
         launch.log_solo("kmer batch")  # (the batch files are one stream's consecutive chunks)
@@ -174,8 +191,8 @@ def batch(input_path: str, output_path: str, k: int, reverse: bool = False, scan
     set_tempdir(tmp)
     os.makedirs(output_path, exist_ok=True)
     try:
-        copy_batches(_batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, False),
-                     output_path, compress)
+        copy_batches(_batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, False,
+                              input_format), output_path, compress)
     except IOError as e:
         logging.error(f"Unable to write to output directory '{output_path}'.\n{e}")
     logging.info("That's all!")
@@ -188,7 +205,7 @@ abundance c, "c<TAB>number of distinct k-mers seen c times".
 Not part of the reference kman CLI (SURVEY.md §8f-1, BASELINE config 5):
 canonical k-mers are min(k-mer, reverse complement); for odd k their counts
 are the `kmer count -r` rows whose sequence is <= its reverse complement.
-The INPUT file can be gzipped.
+INPUT fasta or fastq file, plain or gzipped.
 """)
 @args.input_path()
 @args.output_path(file_okay=True)
@@ -196,14 +213,20 @@ The INPUT file can be gzipped.
 @click.option("--forward", is_flag=True, help="Count forward k-mers instead of canonical ones.")
 @click.option("--max-count", type=click.INT, default=10000, show_default=True,
               help="Abundances from this one up share the last line (>=N).")
-def hist(input_path: str, output_path: str, k: int, forward: bool = False, max_count: int = 10000) -> None:
+@args.input_format()
+def hist(input_path: str, output_path: str, k: int, forward: bool = False, max_count: int = 10000,
+         input_format: str = "auto") -> None:
     input_file_exists(input_path)
     if k <= 1:
         raise AssertionError("k must be >= 1, got %d instead." % k)
+    fastq = launch.distributed() and _is_fastq(input_path, input_format)
+    if fastq and not launch.solo_rank():
+        launch.log_solo("fastq input")
+        return
     if launch.distributed() and k > engine.MAX_K and not launch.solo_rank():
         launch.log_solo("kmer hist k=%d" % k)
         return
-    if launch.distributed() and k <= engine.MAX_K:
+    if launch.distributed() and k <= engine.MAX_K and not fastq:
         # every rank counts its shard's (canonical) k-mers, the spectrum is
         # all-reduced, rank 0 writes it
         src = launch.ShardedSource(engine.default_device(), input_path, k, False)
@@ -216,7 +239,8 @@ def hist(input_path: str, output_path: str, k: int, forward: bool = False, max_c
                 fh.write(engine.format_hist(h))
         logging.info("That's all!")
         return
-    h = engine.abundance_hist(engine.read_input(input_path), k, canonical=not forward, nbins=max_count + 1)
+    h = engine.abundance_hist(engine.read_input(input_path), k, canonical=not forward, nbins=max_count + 1,
+                              fmt=input_format)
     with open(output_path, "wb") as fh:
         fh.write(engine.format_hist(h))
     logging.info("That's all!")

@@ -25,12 +25,14 @@ from . import engine, phases
 
 
 class FastaSource:
-    def __init__(self, dev: engine.Device, text: Optional[bytes], k: int, rc: bool, path: Optional[str] = None):
-        """The k-mer stream of FASTA bytes (`text`), or of the file at `path`
-        (engine.parse_file: chunked pinned reads overlapping the H2D)."""
+    def __init__(self, dev: engine.Device, text: Optional[bytes], k: int, rc: bool, path: Optional[str] = None,
+                 fmt: str = "auto"):
+        """The k-mer stream of FASTA or FASTQ bytes (`text`), or of the file at
+        `path` (engine.parse_file: chunked pinned reads overlapping the H2D);
+        `fmt`: "auto" (engine.sniff_format), "fasta" or "fastq"."""
         engine._check_k(k, wide=True)
         self.dev, self.k, self.rc = dev, k, rc
-        self.parsed = engine.parse_file(dev, path) if text is None else engine.parse(dev, text)
+        self.parsed = engine.parse_file(dev, path, fmt) if text is None else engine.parse(dev, text, fmt)
         engine.check_empty_names(self.parsed, k)
         self.n_kmers = engine.count_kmers(self.parsed, k, rc)
         self._km = {}  # want_pos -> engine.Kmers (stream order)
