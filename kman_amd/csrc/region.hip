@@ -376,6 +376,11 @@ struct PassArgs {
     uint8_t *fail;
     uint32_t fail_div, fail_shift;
     uint32_t big;  // a pass of <= 8 bits on the 1024-thread instance anyway (8192-item tiles: 256-byte digit runs)
+    // 8-byte items on that instance without a staged tile, through 256-byte
+    // lines (rg_pass<..., LN = true>; kman_groups); line1 (KMAN_PASS_LINE1, for
+    // tests): one line per digit at any digit width, so that small inputs take
+    // many placement rounds per tile
+    uint32_t lines, line1;
     // optional (pass 1 of a key round, rg_pass<..., HV = true): the heavy
     // keys of the round, per bucket j of the round an open-addressing table
     // of HV_BSLOTS key rests (the item's key bits, item >> hv_q; HV_EMPTY
@@ -433,16 +438,30 @@ constexpr size_t HVO_TAB = 0, HVO_IDX = HVO_TAB + 256 * HV_BSLOTS * 8, HVO_KEYS 
 // per CU), or 512 threads and up to 8 bits (4096-item tiles and 256 digits'
 // lines, ~69 KiB: two blocks per CU, so one block's loads, rank and scatter
 // run while the other's stores stream)
+// LN (kman_groups' 8-byte items on the 1024-thread instance): no staged tile
+// and 256-byte lines.  The tile's items stay in registers; an item's rank and
+// its digit's running count give its position p in the digit's output stream,
+// and it goes straight to its line slot in LDS.  The 128 KiB of lines are 512
+// lines of 32 items, 2^(9 - bits) of them per digit as a ring over the digit's
+// stream (one line per digit at 9 bits); a line leaves the CU only when whole,
+// as 16 lanes x 16 bytes, so a store phase writes aligned 256-byte runs only.
+// A digit that gets more than its ring holds in one tile is placed in
+// block-uniform rounds (place, barrier, store the whole lines, barrier): their
+// number comes from the tile's largest per-digit line count -- two placements
+// and one store phase on uniform data at any digit width.  Needs C1 a multiple
+// of 32 and a 256-byte aligned output (launch_pass_as checks both).
 constexpr int PT_NT = 1024, PT_SI = 8;
-template <typename TI, typename TO, int NT_ = PT_NT, int RB = R1, bool HV = false, bool ZB = false>
+template <typename TI, typename TO, int NT_ = PT_NT, int RB = R1, bool LN = false, bool HV = false, bool ZB = false>
 __global__ __launch_bounds__(NT_, 4) void rg_pass(PassArgs pa, uint32_t *__restrict__ counter,
                                                  uint32_t *__restrict__ err, uint64_t *__restrict__ stp) {
     constexpr int NT = NT_, SI = HV ? PT_SI - 1 : PT_SI, TILE = NT * SI, NWAVE = NT / 64;  // (HV: 7 items, no spills)
+    static_assert(!LN || (!HV && !ZB && sizeof(TI) == 8 && sizeof(TO) == 8 && NT == 1024 && RB == 512),
+                  "lines of 32 items: the 8-byte, 1024-thread, 512-digit instance");
     // items per write-combining line (128 bytes)
     constexpr uint32_t WLB = sizeof(TO) == 8 ? 4 : 5, WL = 1u << WLB, WM = WL - 1;
     static_assert(NT >= RB && NT / WL <= RB, "a thread per digit");
-    __shared__ __attribute__((aligned(16))) TI skeys[TILE];
-    __shared__ __attribute__((aligned(16))) uint64_t wcb_[RB * 16];  // 128 bytes per digit
+    __shared__ __attribute__((aligned(16))) TI skeys[LN ? 1 : TILE];
+    __shared__ __attribute__((aligned(16))) uint64_t wcb_[LN ? RB * 32 : RB * 16];  // 128 bytes per digit (LN: 256)
     TO(*const wcb)[WL] = reinterpret_cast<TO(*)[WL]>(wcb_);  // the pending items of digit d at wcb[d][pos % WL]
     // pending items leave 16 lanes per digit (one line per quarter wave), EPL
     // items per lane: a 4-byte item's lane stores two as one 8-byte store
@@ -461,9 +480,10 @@ __global__ __launch_bounds__(NT_, 4) void rg_pass(PassArgs pa, uint32_t *__restr
     // items << 32) | the output index of tile item 0 relative to the chain's
     // first sub-region (digit d's sub-region is d * gsub * H after it, and
     // C1 is a multiple of 16, so the low 4 bits are the line slot)
-    __shared__ uint64_t qpar[RB];
+    __shared__ uint64_t qpar[LN ? 1 : RB];
     __shared__ uint32_t thist[RB];
-    __shared__ uint32_t lstart[RB];
+    __shared__ uint32_t lstart[LN ? 1 : RB];
+    __shared__ uint32_t s_nl;  // LN: the most lines any digit completes in this tile
     __shared__ uint32_t run[RB];  // the chain's running count per digit
     __shared__ uint32_t lds_scan[NWAVE];
     __shared__ uint32_t s_items;
@@ -589,6 +609,7 @@ __global__ __launch_bounds__(NT_, 4) void rg_pass(PassArgs pa, uint32_t *__restr
             // (double-buffered counts, so that neither this clear nor the
             // update below needs its barrier: no faster, 3.50 vs 3.41-3.50 ms)
             if (threadIdx.x < RB) thist[threadIdx.x] = 0;
+            if (LN && threadIdx.x == 0) s_nl = 0;
             __syncthreads();
             const uint32_t t0 = r * TILE;
             const uint32_t n = items - t0 < (uint32_t)TILE ? items - t0 : (uint32_t)TILE;
@@ -650,50 +671,119 @@ __global__ __launch_bounds__(NT_, 4) void rg_pass(PassArgs pa, uint32_t *__restr
                 for (int i = 0; i < SI; i++) rank[i] = (vm >> i) & 1u ? atomicAdd(&thist[PDIGIT(key[i])], 1u) : 0u;
             }
             __syncthreads();
-            const uint32_t ls = block_exclusive_scan1<NT>(threadIdx.x < RB ? thist[threadIdx.x] : 0u, SumU32(), 0u,
-                                                          lds_scan, (uint32_t *)nullptr);
-            if (threadIdx.x < RB) lstart[threadIdx.x] = ls;
-            __syncthreads();
+            if constexpr (LN) {
+                // digit d's ring: its 2^lb lines, RING items; stream line g
+                // (items [32 g, 32 g + 32) of d's sub-region) sits in line
+                // (d << lb) | (g & lm); the first line not yet stored is run[d] >> 5
+                // (line1, a test setting: one line per digit at any width)
+                const uint32_t lb = pa.line1 ? 0u : 9u - bits, lm = (1u << lb) - 1, RING = 32u << lb;
+                if (threadIdx.x < RB) {
+                    struct MaxU32 {
+                        KMAN_DEV uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
+                    };
+                    const uint32_t rn = run[threadIdx.x];
+                    const uint32_t nl = ((rn + thist[threadIdx.x]) >> 5) - (rn >> 5);
+                    const uint32_t m = wave_inclusive_scan(nl, MaxU32(), 0u);
+                    if (lane == 63 && m) atomicMax(&s_nl, m);
+                }
+                // rank[i] <- the item's placement round << 14 | its ring slot
 #pragma unroll
-            for (int i = 0; i < SI; i++)
-                if ((vm >> i) & 1u) skeys[lstart[PDIGIT(key[i])] + rank[i]] = key[i];
-            // (HV: the tile's items that stay, packed at the front of skeys)
-            const uint32_t nk = HV ? lstart[RB - 1] + thist[RB - 1] : n;
-            __syncthreads();
-            RSTAMP(r, 1);
-            // a digit whose partial line completes in this tile: its pending
-            // items go out first, 16 lanes per digit (one line per quarter
-            // wave, so a store covers 4 lines)
-            // (the LDS reads of this loop and the store loop below issued
-            // first, back to back: 3.39 vs 3.31 ms, `r04o_pipe_ab.txt`)
+                for (int i = 0; i < SI; i++) {
+                    const uint32_t rn = run[PDIGIT(key[i])], p = rn + rank[i];
+                    rank[i] = ((((p >> 5) - (rn >> 5)) >> lb) << 14) | (p & (RING - 1));
+                }
+                auto place = [&](uint32_t round) {
 #pragma unroll
-            for (uint32_t it = 0; it < RB / (NT / 16); it++) {  // (a constant trip count: unrolled)
-                const uint32_t d = (threadIdx.x >> 4) + it * (NT / 16);
-                const uint32_t j = (threadIdx.x & 15u) * EPL, rn = run[d], p = rn & WM;
-                if (j < p && ((rn + thist[d]) >> WLB) > (rn >> WLB) && rn - p + j < C1)
-                    put_pending(obase0 + d * dstride + rn - p + j, &wcb[d][j], j + 1 < p && rn - p + j + 1 < C1);
-            }
-            if (threadIdx.x < RB) {
-                // item q of digit d goes to position at = q + off; whole lines
-                // end at fe; positions >= C1 are dropped (an overflowing
-                // region raises ERR_REGION, so where its items go is moot)
-                const uint32_t d = threadIdx.x, rn = run[d], off = rn - lstart[d];
-                const int32_t fe = (int32_t)((rn + thist[d]) & ~WM);
-                const int32_t qlim = (fe < (int32_t)C1 ? fe : (int32_t)C1) - (int32_t)off;
-                qpar[d] = ((uint64_t)(uint32_t)qlim << 32) | (d * dstride + off);
-            }
-            __syncthreads();  // those wcb reads before the leftovers below
-            // items of whole lines to HBM, the new partial line to LDS
+                    for (int i = 0; i < SI; i++)
+                        if (((vm >> i) & 1u) && (rank[i] >> 14) == round)
+                            wcb_[PDIGIT(key[i]) * RING + (rank[i] & 0x3fffu)] = key[i];
+                };
+                place(0);
+                __syncthreads();
+                RSTAMP(r, 1);
+                // the tile completes at most mx lines of a digit: nst store
+                // phases (a ring's worth of lines each), npl placements
+                const uint32_t mx = s_nl, nst = (mx + lm) >> lb, npl = (mx >> lb) + 1;
+                for (uint32_t ph = 0; ph < nst; ph++) {
+                    // the lines whole after placement ph, 16 lanes x 16 bytes
+                    // each (a wave's store covers 4 lines); lines at or past
+                    // the capacity stay (C1 is a multiple of 32)
+                    // (SB lines' LDS reads back to back, then their stores; all
+                    // eight at once spill)
+                    constexpr uint32_t SB = 4;
 #pragma unroll
-            for (int rr = 0; rr < SI; rr++) {
-                const uint32_t q = threadIdx.x + rr * NT;
-                if (q < nk) {
-                    const uint64_t kk = skeys[q];
-                    const uint32_t d = PDIGIT(kk);
-                    const uint64_t qp = qpar[d];
-                    const uint32_t rel = (uint32_t)qp + q;
-                    if ((int32_t)q < (int32_t)(qp >> 32)) obase0[rel] = (TO)kk;
-                    else wcb[d][rel & WM] = (TO)kk;
+                    for (uint32_t i0 = 0; i0 < RB / (NT / 16); i0 += SB) {
+                        uint4 v[SB];
+                        uint32_t at[SB];
+#pragma unroll
+                        for (uint32_t it = 0; it < SB; it++) {
+                            const uint32_t x = (threadIdx.x >> 4) + (i0 + it) * (NT / 16), d = x >> lb;
+                            const uint32_t rn = run[d], g0 = (rn >> 5) + (ph << lb), g = g0 + ((x - g0) & lm);
+                            const bool whole = g < ((rn + thist[d]) >> 5) && g * 32u < C1;
+                            at[it] = whole ? d * dstride + g * 32u + (threadIdx.x & 15u) * 2u : ~0u;
+                            v[it] = *reinterpret_cast<const uint4 *>(&wcb_[x * 32u + (threadIdx.x & 15u) * 2u]);
+                        }
+                        // (keeps the reads here: sunk into the branches below,
+                        // each store waits for its own read)
+#pragma unroll
+                        for (uint32_t it = 0; it < SB; it++)
+                            asm volatile("" : "+v"(v[it].x), "+v"(v[it].y), "+v"(v[it].z), "+v"(v[it].w));
+#pragma unroll
+                        for (uint32_t it = 0; it < SB; it++)
+                            if (at[it] != ~0u) *reinterpret_cast<uint4 *>(obase0 + at[it]) = v[it];
+                    }
+                    if (ph + 1 < npl) {
+                        __syncthreads();  // those line reads before the next placement
+                        place(ph + 1);
+                        if (ph + 1 < nst) __syncthreads();
+                    }
+                }
+            } else {
+                const uint32_t ls = block_exclusive_scan1<NT>(threadIdx.x < RB ? thist[threadIdx.x] : 0u, SumU32(), 0u,
+                                                              lds_scan, (uint32_t *)nullptr);
+                if (threadIdx.x < RB) lstart[threadIdx.x] = ls;
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < SI; i++)
+                    if ((vm >> i) & 1u) skeys[lstart[PDIGIT(key[i])] + rank[i]] = key[i];
+                // (HV: the tile's items that stay, packed at the front of skeys)
+                const uint32_t nk = HV ? lstart[RB - 1] + thist[RB - 1] : n;
+                __syncthreads();
+                RSTAMP(r, 1);
+                // a digit whose partial line completes in this tile: its pending
+                // items go out first, 16 lanes per digit (one line per quarter
+                // wave, so a store covers 4 lines)
+                // (the LDS reads of this loop and the store loop below issued
+                // first, back to back: 3.39 vs 3.31 ms, `r04o_pipe_ab.txt`)
+#pragma unroll
+                for (uint32_t it = 0; it < RB / (NT / 16); it++) {  // (a constant trip count: unrolled)
+                    const uint32_t d = (threadIdx.x >> 4) + it * (NT / 16);
+                    const uint32_t j = (threadIdx.x & 15u) * EPL, rn = run[d], p = rn & WM;
+                    if (j < p && ((rn + thist[d]) >> WLB) > (rn >> WLB) && rn - p + j < C1)
+                        put_pending(obase0 + d * dstride + rn - p + j, &wcb[d][j], j + 1 < p && rn - p + j + 1 < C1);
+                }
+                if (threadIdx.x < RB) {
+                    // item q of digit d goes to position at = q + off; whole lines
+                    // end at fe; positions >= C1 are dropped (an overflowing
+                    // region raises ERR_REGION, so where its items go is moot)
+                    const uint32_t d = threadIdx.x, rn = run[d], off = rn - lstart[d];
+                    const int32_t fe = (int32_t)((rn + thist[d]) & ~WM);
+                    const int32_t qlim = (fe < (int32_t)C1 ? fe : (int32_t)C1) - (int32_t)off;
+                    qpar[d] = ((uint64_t)(uint32_t)qlim << 32) | (d * dstride + off);
+                }
+                __syncthreads();  // those wcb reads before the leftovers below
+                // items of whole lines to HBM, the new partial line to LDS
+#pragma unroll
+                for (int rr = 0; rr < SI; rr++) {
+                    const uint32_t q = threadIdx.x + rr * NT;
+                    if (q < nk) {
+                        const uint64_t kk = skeys[q];
+                        const uint32_t d = PDIGIT(kk);
+                        const uint64_t qp = qpar[d];
+                        const uint32_t rel = (uint32_t)qp + q;
+                        if ((int32_t)q < (int32_t)(qp >> 32)) obase0[rel] = (TO)kk;
+                        else wcb[d][rel & WM] = (TO)kk;
+                    }
                 }
             }
             // the next tile's loads behind the stores (issued before the
@@ -708,13 +798,29 @@ __global__ __launch_bounds__(NT_, 4) void rg_pass(PassArgs pa, uint32_t *__restr
         // the chain's sub-region counts (every digit, also of empty chains)
         __syncthreads();
         // the last partial lines, 16 lanes per digit
+        if constexpr (LN) {
+            // (the one line of a digit's ring that holds its stream's open line)
+            const uint32_t lb = pa.line1 ? 0u : 9u - bits, lm = (1u << lb) - 1;
+            // (once per chain; unrolled, its eight addresses are kept, spilled, over the tile loop)
+#pragma unroll 1
+            for (uint32_t it = 0; it < RB / (NT / 16); it++) {
+                const uint32_t x = (threadIdx.x >> 4) + it * (NT / 16), d = x >> lb;
+                const uint32_t j = (threadIdx.x & 15u) * 2u, rn = d < radix ? run[d] : 0u, p = rn & 31u;
+                if (j < p && ((rn >> 5) & lm) == (x & lm) && rn - p < C1) {
+                    TO *const dst = obase0 + d * dstride + rn - p + j;
+                    if (j + 1 < p) *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(&wcb_[x * 32u + j]);
+                    else *dst = wcb_[x * 32u + j];
+                }
+            }
+        } else {
 #pragma unroll
-        for (uint32_t it = 0; it < RB / (NT / 16); it++) {
-            const uint32_t d = (threadIdx.x >> 4) + it * (NT / 16);
-            const uint32_t j = (threadIdx.x & 15u) * EPL, rn = run[d], p = rn & WM;
-            if (j < p && rn - p + j < C1)
-                put_pending(static_cast<TO *>(pa.out) + SUBREG(d) * C1 + rn - p + j, &wcb[d][j],
-                            j + 1 < p && rn - p + j + 1 < C1);
+            for (uint32_t it = 0; it < RB / (NT / 16); it++) {
+                const uint32_t d = (threadIdx.x >> 4) + it * (NT / 16);
+                const uint32_t j = (threadIdx.x & 15u) * EPL, rn = run[d], p = rn & WM;
+                if (j < p && rn - p + j < C1)
+                    put_pending(static_cast<TO *>(pa.out) + SUBREG(d) * C1 + rn - p + j, &wcb[d][j],
+                                j + 1 < p && rn - p + j + 1 < C1);
+            }
         }
         if (threadIdx.x < RB) {
             const uint32_t d = threadIdx.x;
@@ -1423,6 +1529,8 @@ int make_plan(uint64_t n_bases, uint32_t k, uint32_t flags, int mode, RegionPlan
     if (nb0 * RS * p.C0 >= (1ull << 32)) return KMAN_EFALLBACK;  // (32-bit item indices)
     const uint64_t e1 = p.W >> (G1 + b2);
     uint64_t c1 = ceil_div(e1 + e1 / 2 + 512, 64) * 64;
+    // (a multiple of 32 either way, and off_r1 of 512 bytes: pass 1's 256-byte lines)
+    static_assert(FCAP % 32 == 0, "a sub-region ends on a 256-byte line");
     p.C1 = c1 < (uint64_t)FCAP ? c1 : (uint64_t)FCAP;
     // pass 1 runs H = 2 block-owned chains per bucket (its first and second
     // half of tiles) into H sub-regions per region that the finish
@@ -1444,17 +1552,17 @@ template <typename TI, typename TO>
 void launch_pass_as(kman_ctx *ctx, const PassArgs &pa, uint32_t *counter, uint64_t *stp) {
     if constexpr (sizeof(TI) == 8) {
         if (pa.hv_tab) {  // (pass 1 of a key round with heavy keys: 9 bits, the 1024-thread instance)
-            const uint32_t grid = (uint32_t)kman_persistent_grid(ctx, (const void *)rg_pass<TI, TO, PT_NT, R1, true>,
+            const uint32_t grid = (uint32_t)kman_persistent_grid(ctx, (const void *)rg_pass<TI, TO, PT_NT, R1, false, true>,
                                                                  PT_NT, (uint64_t)pa.nbk * pa.H);
-            hipLaunchKernelGGL((rg_pass<TI, TO, PT_NT, R1, true>), dim3(grid), dim3(PT_NT), 0, ctx->stream, pa, counter,
+            hipLaunchKernelGGL((rg_pass<TI, TO, PT_NT, R1, false, true>), dim3(grid), dim3(PT_NT), 0, ctx->stream, pa, counter,
                                ctx->d_err, stp);
             return;
         }
     }
     if (pa.bits == 0) {  // (a 0-bit pass: pass 1b merging the sources' sub-regions -- its own instance)
-        const uint32_t grid = (uint32_t)kman_persistent_grid(ctx, (const void *)rg_pass<TI, TO, 512, 256, false, true>,
+        const uint32_t grid = (uint32_t)kman_persistent_grid(ctx, (const void *)rg_pass<TI, TO, 512, 256, false, false, true>,
                                                              512, (uint64_t)pa.nbk * pa.H);
-        hipLaunchKernelGGL((rg_pass<TI, TO, 512, 256, false, true>), dim3(grid), dim3(512), 0, ctx->stream, pa, counter,
+        hipLaunchKernelGGL((rg_pass<TI, TO, 512, 256, false, false, true>), dim3(grid), dim3(512), 0, ctx->stream, pa, counter,
                            ctx->d_err, stp);
         return;
     }
@@ -1467,6 +1575,18 @@ void launch_pass_as(kman_ctx *ctx, const PassArgs &pa, uint32_t *counter, uint64
                            ctx->d_err, stp);
         return;
     }
+#ifndef KMAN_PASS_TILE  // (-DKMAN_PASS_TILE: the staged-tile body for these items too, for A/B)
+    if constexpr (sizeof(TI) == 8 && sizeof(TO) == 8) {
+        // whole 256-byte lines: every sub-region starts on one and ends on one
+        if (pa.lines && pa.C1 % 32 == 0 && (uintptr_t)pa.out % 256 == 0) {
+            const uint32_t grid = (uint32_t)kman_persistent_grid(
+                ctx, (const void *)rg_pass<TI, TO, PT_NT, R1, true>, PT_NT, (uint64_t)pa.nbk * pa.H);
+            hipLaunchKernelGGL((rg_pass<TI, TO, PT_NT, R1, true>), dim3(grid), dim3(PT_NT), 0,
+                               ctx->stream, pa, counter, ctx->d_err, stp);
+            return;
+        }
+    }
+#endif
     const uint32_t grid =
         (uint32_t)kman_persistent_grid(ctx, (const void *)rg_pass<TI, TO>, PT_NT, (uint64_t)pa.nbk * pa.H);
     hipLaunchKernelGGL((rg_pass<TI, TO>), dim3(grid), dim3(PT_NT), 0, ctx->stream, pa, counter, ctx->d_err, stp);
@@ -1768,6 +1888,8 @@ int groups_tail(kman_ctx *ctx, const GroupsCall &g, int mode, uint64_t *d_okeys,
         pa.C1 = p.C1h;
         pa.cnt1 = g.c1;
         pa.big = 1;
+        pa.lines = 1;
+        pa.line1 = getenv("KMAN_PASS_LINE1") ? 1 : 0;
         launch_pass(ctx, pa, counter, stamps[1], false, narrow4);
         HIP_TRY(ctx, hipGetLastError());
     }
