@@ -142,7 +142,7 @@ constexpr uint32_t SPIN_LIMIT = 1u << 20; // ~1 s of polling; a hit is an engine
 
 // true when this waiter must give up: its own bound is spent, or another wave
 // already flagged a fault (so one fault does not cascade into serial
-// timeouts).  Bit 8 (region.hip's ERR_REGION, a region that would overflow)
+// timeouts).  Bit 8 (region.h's ERR_REGION, a region that would overflow)
 // is not a fault: the round path keeps every other region's rows, so their
 // look-backs must still complete.
 KMAN_DEV bool spin_give_up(uint32_t &spins, uint32_t *err, uint32_t code) {

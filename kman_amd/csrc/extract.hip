@@ -112,13 +112,6 @@ __global__ __launch_bounds__(ET) void extract_kernel(const uint8_t *__restrict__
         const uint32_t cnt = __popc(vf) + (RC && !CANON ? __popc(vr) : 0);
         uint32_t total;
         const uint32_t loff = block_exclusive_scan<ET>(cnt, SumU32(), 0u, lds_scan, &total);
-#if defined(KMAN_ABL) && (KMAN_ABL & 32)
-        // ablation build only: no look-back (wrong offsets, measures the rest)
-        if (threadIdx.x == 0) {
-            lds_base = tb;
-            st_store(&status[tile], st_make(ST_INCL, epoch, tb + total));
-        }
-#else
         if (pmap) {
             // marked windows (a redo that sorts them next): places by one
             // atomic per tile that has any, no look-back chain through the
@@ -129,7 +122,6 @@ __global__ __launch_bounds__(ET) void extract_kernel(const uint8_t *__restrict__
             const uint64_t b = wave_lookback<0>(status, tile, total, epoch, err);
             if (threadIdx.x == 0) lds_base = b;
         }
-#endif
         // stage keys at compacted offsets
         {
             uint32_t o = loff;
@@ -144,11 +136,7 @@ __global__ __launch_bounds__(ET) void extract_kernel(const uint8_t *__restrict__
         for (uint32_t q = threadIdx.x; q < total; q += ET) {
             const uint64_t key = skeys[q];
             if (base + q < cap) keys[base + q] = key;  // (a key range past cap: counted, not written)
-#if defined(KMAN_ABL) && (KMAN_ABL & 64)
-            if (false) {
-#else
             if (hist) {
-#endif
                 for (int p = 0; p < plan.npass; p++) {
                     const uint32_t d = (uint32_t)(key >> plan.shift[p]) & ((1u << plan.bits[p]) - 1);
                     atomicAdd(&lhist[p][d], 1u);
@@ -228,12 +216,9 @@ __global__ __launch_bounds__(ET) void count_kernel(const uint8_t *__restrict__ c
 // valid-window count and the radix-digit histograms of every pass of `plan`,
 // no keys written: the pre-pass of the fused extract + first sort pass
 // (kman_extract_sorted needs the global digit-0 counts before any key moves)
-#ifndef KMAN_KH_C
-#define KMAN_KH_C 2
-#endif
 // Counters are spread over KH_C copies (lane & (KH_C - 1)) interleaved per bin,
 // so same-digit lanes of one wave update different words.
-constexpr int KH_C = KMAN_KH_C;
+constexpr int KH_C = 2;
 
 template <int EI, bool RC, int NP>
 __global__ __launch_bounds__(ET) void kmer_hist_kernel(const uint8_t *__restrict__ codes, uint64_t n_bases,
@@ -266,11 +251,6 @@ __global__ __launch_bounds__(ET) void kmer_hist_kernel(const uint8_t *__restrict
         acc += __popc(valid) * (RC ? 2 : 1);
         // EI windows of a thread never straddle a window segment (seg_w % EI == 0)
         const uint32_t wseg = (uint32_t)(p0 / seg_w);
-#if defined(KMAN_ABL) && (KMAN_ABL & 128)
-        // ablation build only: no histogram atomics
-        if (valid == 0x12345) acc += kf[3] ^ kr[5] ^ wseg;
-        else continue;
-#endif
 #pragma unroll
         for (int j = 0; j < EI; j++) {
             if ((valid >> j) & 1u) {

@@ -1,5 +1,5 @@
 // onesweep.h — decoupled look-back pieces shared by the onesweep digit passes
-// (sort.hip) and the region passes (region.hip).  Status words are
+// (sort.hip) and the region passes (region.h).  Status words are
 // flag:2 | epoch:6 | value:56 (common.h), RADIX per tile, digit-major inside.
 #pragma once
 #include "common.h"
@@ -7,10 +7,7 @@
 namespace {
 
 constexpr int RADIX = 256;
-#ifndef KMAN_LB
-#define KMAN_LB 8
-#endif
-constexpr int LB = KMAN_LB;  // predecessor status words fetched per look-back round
+constexpr int LB = 8;  // predecessor status words fetched per look-back round
 
 
 // publish a tile's digit count: inclusive for a chain's first tile

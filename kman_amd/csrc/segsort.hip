@@ -35,17 +35,10 @@
 
 namespace {
 
-#ifndef KMAN_FT
-#define KMAN_FT 512
-#endif
-#ifndef KMAN_FC
-#define KMAN_FC 5120
-#define KMAN_FR 6144
-#endif
-constexpr int FT = KMAN_FT;    // threads per chunk
+constexpr int FT = 512;        // threads per chunk
 constexpr int FW = FT / 64;    // waves
-constexpr int FC = KMAN_FC;    // chunk: segments that start here are owned
-constexpr int FR = KMAN_FR;    // region capacity: chunk + tail of its last segment
+constexpr int FC = 5120;       // chunk: segments that start here are owned
+constexpr int FR = 6144;       // region capacity: chunk + tail of its last segment
 constexpr int FI = FR / FT;    // items per thread
 constexpr int PI = FC / FT + 1;  // rounds loaded up front: the chunk and the next FT keys
 constexpr int NWORD = FR / 64;   // segment-start mask words
@@ -477,10 +470,6 @@ __global__ __launch_bounds__(FT) void segfin_kernel(uint64_t *__restrict__ keys,
                 __syncthreads();
             }
             const uint32_t s0 = lead_pre ? 1u : 0u, s1 = nsegs - (trail_pre ? 1u : 0u);
-#if defined(KMAN_ABL) && (KMAN_ABL & 8)
-            // ablation build only: no segment sort (wrong order, measures the rest)
-            if (false)
-#endif
             for (uint32_t j = s0 + (uint32_t)w; j < s1; j += FW) {
                 const uint32_t sa = seg_start(j), sb = seg_start(j + 1);
                 if (sb - sa < 2) {

@@ -243,10 +243,6 @@ __global__ __launch_bounds__(NT, MINW) void onesweep_pass(const uint64_t *__rest
         lp[i] = valid ? lstart[d] + whist[w][d] + rank[i] : 0xffffffffu;
         if (valid) skeys[lp[i]] = key[i];
     }
-#if defined(KMAN_ABL) && (KMAN_ABL & 1)
-    // ablation build only: no look-back (wrong offsets, measures the rest)
-    if (d0 < radix) gstart[d0] = bb[d0] + (uint64_t)jj * TILE / radix - ls;
-#else
     if constexpr (EARLY) {
         // several lanes per digit walk the chain (see group_lookback)
         const uint32_t tpd = NT / radix >= 4 ? 4 : (NT / radix >= 2 ? 2 : 1);
@@ -262,7 +258,6 @@ __global__ __launch_bounds__(NT, MINW) void onesweep_pass(const uint64_t *__rest
         const uint64_t excl = digit_lookback<EARLY>(status + d0, tile, first, tot, epoch, err);
         gstart[d0] = bb[d0] + excl - ls;
     }
-#endif
     __syncthreads();
     STAMP(3);
     const uint32_t cnt = (uint32_t)(n - tb < (uint64_t)TILE ? n - tb : (uint64_t)TILE);
@@ -274,12 +269,7 @@ __global__ __launch_bounds__(NT, MINW) void onesweep_pass(const uint64_t *__rest
         if (q < cnt) {
             const uint64_t kk = skeys[q];
             const uint32_t d = DIGIT(kk);
-#if defined(KMAN_ABL) && (KMAN_ABL & 2)
-            // ablation build only: contiguous writes instead of the digit scatter
-            kout[tb + q] = kk + gstart[d];
-#else
             kout[gstart[d] + q] = kk;
-#endif
             if constexpr (HAS_V) dq[r] = (uint8_t)d;
         }
     }
@@ -749,25 +739,8 @@ extern "C" int kman_sort_range(kman_ctx *ctx, uint64_t *d_keys, uint64_t *d_keys
     }
     (void)scr;
     const uint64_t *hs = d_hist ? nullptr : h_seg;
-    static const int cfg = [] {
-        const char *e = getenv("KMAN_SORT_CFG");  // tuning experiments only
-        return e ? atoi(e) : 0;
-    }();
-    if (cfg) nseg = 1, hs = nullptr;  // (tile-size experiments: one chain, global bases)
-#define KMAN_DV(NT_, SI_, ...)                                                                                     \
-    KMAN_TRY((dispatch_vals<NT_, SI_, ##__VA_ARGS__>(ctx, d_keys, d_keys_alt, d_vals, d_vals_alt, val_bytes, n, np, \
-                                                      sh, bi, h_hist, hs, nseg, nullptr, 0, result_in_alt)))
-    switch (cfg) {
-        case 1: KMAN_DV(512, 12); break;
-        case 2: KMAN_DV(256, 24); break;
-        case 3: KMAN_DV(1024, 8); break;
-        case 4: KMAN_DV(256, 16); break;
-        case 6: KMAN_DV(256, 16, false); break;
-        case 7: KMAN_DV(512, 12, false); break;
-        case 5: KMAN_DV(256, 8); break;
-        default: KMAN_DV(512, 16); break;
-    }
-#undef KMAN_DV
+    KMAN_TRY((dispatch_vals<512, 16>(ctx, d_keys, d_keys_alt, d_vals, d_vals_alt, val_bytes, n, np, sh, bi, h_hist, hs,
+                                     nseg, nullptr, 0, result_in_alt)));
     return kman_check_device_error(ctx);
 }
 

@@ -751,7 +751,7 @@ def rle_uniq(km: Kmers, dev: Device) -> UniqResult:
 
 def groups(p: Parsed, k: int, rc: bool, mode: str, canonical: bool = False, mixed: bool = False):
     """kman_groups: count / uniq of the whole stream straight from the codes
-    (region.hip).  Returns a CountResult / UniqResult, or None when the input
+    (region.h).  Returns a CountResult / UniqResult, or None when the input
     is outside the region path (kman_groups_plan / a region overflow said
     KMAN_EFALLBACK): the caller then runs extract_sorted + rle_*."""
     L, dev = N.lib(), p.dev

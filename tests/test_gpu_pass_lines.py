@@ -1,4 +1,4 @@
-"""GPU parity of kman_groups' digit pass without a staged tile (region.hip,
+"""GPU parity of kman_groups' digit pass without a staged tile (region_pass.hip,
 rg_pass<..., LN = true>): items ranked from registers into 256-byte
 write-combining lines, whole lines stored in block-uniform rounds.
 
@@ -78,7 +78,7 @@ def _oracle(text, k, rc, mode):
 
 
 def _plan(W):
-    """region.hip's make_plan for W k-mer slots: pass-1 bits and sub-region
+    """region_groups.hip's make_plan for W k-mer slots: pass-1 bits and sub-region
     capacity."""
     b2 = 1
     while b2 < 9 and (W >> (8 + b2)) > 6144:

@@ -1,4 +1,4 @@
-"""GPU parity of the region path (kman_groups, kman_amd/csrc/region.hip):
+"""GPU parity of the region path (kman_groups, kman_amd/csrc/region.h):
 count / uniq of a whole stream straight from the codes.
 
 Bar: bit-exact against the numpy restatement of the reference's path
@@ -88,7 +88,7 @@ def test_groups_matches_oracle(dev, golden_inputs, monkeypatch, k, rc, mode, che
         wb = c_uint64(0)
         inside = N.lib().kman_groups_plan(n_bases, k, flags, m, byref(wb)) == N.KMAN_OK
         # outside: 2k - 8 key bits + the pos bits exceed one u64 item, or no
-        # key bits left below the 8 + b2 region bits (b2 as region.hip picks it)
+        # key bits left below the 8 + b2 region bits (b2 as region_groups.hip picks it)
         W = n_bases * (2 if rc else 1)
         q = max(1, int(W - 1).bit_length()) if mode == "uniq" else 0
         b2 = 1

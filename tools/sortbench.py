@@ -2,7 +2,7 @@
 """Micro-benchmark of kman_sort on device-resident random keys (+ u32 payload).
 
 Times every onesweep pass with the library's HIP-event timer.  KMAN_LIB may
-point at an ablation build (see kman_amd/csrc/Makefile ABL=...)."""
+point at another build of the library."""
 import argparse, ctypes, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
