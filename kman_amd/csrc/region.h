@@ -50,7 +50,11 @@ constexpr int RT = 512;           // threads of passes 0 and 1
 constexpr int RS = 64;            // position segments of pass 0 (one wave of counts)
 constexpr int FCAP = 8704;        // finish capacity: 68 KiB of 8-byte items
 constexpr uint32_t ERR_REGION = 1u << 8;  // a region would overflow (not an engine fault)
-constexpr uint32_t ERR_EARLY = 1u << 9;   // the uniq finish's early row count was not its rows'
+// the uniq finish's early row count was not its rows', or a singleton mark
+// not the row its sorted keys give: raised by the checked kernels
+// (KMAN_RG_CHECK) only -- the plain kernel's rows ARE the marked items and
+// their count (its compacting last pass), so it has nothing to compare
+constexpr uint32_t ERR_EARLY = 1u << 9;
 constexpr uint32_t B1 = 8;        // pass-0 digit: top 8 key bits
 // kman_groups' pass-0 bits.  (9, with 9 more in pass 1, leaves regions of ~3.8
 // K items per 1 G k-mers that a GCAP finish holds in 40 KiB -- three blocks

@@ -30,7 +30,9 @@ constexpr int FWORD = FRAD / 2;   // per-wave counters: two u16 per word
 // CHK (uniq): the early row count (below) is checked against the rows the
 // sorted keys give -- per thread, the singleton marks against heads & tails
 // computed from the keys -- and a disagreement raises ERR_EARLY; CHK = 2 also
-// flips one mark of region `hook` (a test of the check itself).
+// flips one mark of region `hook` (a test of the check itself).  CHK = 0 with
+// atomic ranks: the last pass moves the marked items only and its scatter is
+// the compacted row list (COMPACT below).
 enum { RG_COUNT = 1, RG_UNIQ = 2 };
 
 // waves per SIMD the launch bounds ask for: 8-byte items of a GCAP region
@@ -169,6 +171,16 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
     // (the round path's items carry the source rank in the 9 bits at
     // tag_shift, read as 8 bits below: bit 63 is free there as well)
     const bool early = MODE == RG_UNIQ && (!tag_shift || tag_shift + 8 <= 63) && np >= 2;
+    // COMPACT (the plain uniq finish with atomic ranks): which items are rows
+    // and how many is settled by early_marks() before the last pass, so that
+    // pass ranks and scatters the marked items only -- the marked keys are
+    // distinct, the pass is stable and the earlier passes ordered the low
+    // bits -- and leaves s[0, etot) holding the region's rows compacted in key
+    // order: no run-length pass, no offset scan, no staging, and the look-back
+    // runs inside the pass (compact_lookback).  The checked instances sort every
+    // item and compare the marks with the rows the sorted keys give; a call
+    // where `early` does not hold takes the run-length pass here as well.
+    constexpr bool COMPACT = MODE == RG_UNIQ && CHK == 0 && ATOMIC && !NARROW;
     uint32_t etot = 0;
     uint32_t at = 0;
     uint32_t p0 = 0;
@@ -295,6 +307,28 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
             (void)block_exclusive_scan1<NT>((uint32_t)__popc(S), SumU32(), 0u, lds_scan2, &etot);
             if (t == 0) publish_agg<0>(status, r, etot, epoch);
     };
+    // item i of the thread takes part in a pass: inside the region, and in the
+    // compacting last pass (cp) marked (an item past m holds 0: no mark)
+    auto live = [&](int i, bool cp) -> bool {
+        if constexpr (COMPACT) {
+            if (cp) return (int32_t)((uint64_t)x[i] >> 32) < 0;
+        }
+        return pw + i * 64 < m;
+    };
+    // the compacting pass's look-back: the rows will be s[0, etot), and the
+    // region's predecessors published their counts a pass ago, so the last
+    // wave (the one with the fewest items: a region fills 7 of its 8 waves
+    // and a little) looks back once the digit starts are in place, while the
+    // other waves read their slots and scatter; the pass's last barrier
+    // publishes s_out.  (By wave 0 after its scatter, every wave waiting at
+    // that barrier for the status loads: finish 5.03-5.04 vs 4.91-4.95 ms,
+    // `finish_compact_ab.txt`)
+    auto compact_lookback = [&]() {
+        if (w == NW_ - 1) {
+            const uint64_t ob = wave_lookback_published<0>(status, r, etot, epoch, err);
+            if (lane == 0) s_out = ob;
+        }
+    };
     if constexpr (U32C) {
         // the 8-byte-item finish: a first pass by up to 11 bits on ONE
         // block-wide array of u32 counters (unstable, as a first LSD pass may
@@ -305,6 +339,7 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
         uint32_t *const flat = &wh[0][0];
         for (uint32_t p = 0; p < np; p++) {
             const bool blk = p == 0;
+            const bool cp = COMPACT && early && p + 1 == np;  // (block-uniform)
             const uint32_t bw = blk ? rest - 8 * (np - 1) : 8u;
             const uint32_t sh = Q + at, dm = (1u << bw) - 1;
             at += bw;
@@ -321,7 +356,7 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
             uint32_t rk[IPT];
 #pragma unroll
             for (int i = 0; i < IPT; i++) {
-                const bool valid = pw + i * 64 < m;
+                const bool valid = live(i, cp);
                 const uint32_t d = (uint32_t)(x[i] >> sh) & dm;
                 rk[i] = atomicAdd(&wc[valid ? d : nd + lane], 1u);
             }
@@ -355,6 +390,7 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
                 }
             }
             __syncthreads();
+            if (cp) compact_lookback();
 #pragma unroll
             for (int i = 0; i < IPT; i++) rk[i] += wc[(uint32_t)(x[i] >> sh) & dm];
             // (only the items: the slot grid past m is 12-14 % of a region's
@@ -362,7 +398,7 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
             // the branches: 5.72 vs 5.21 ms, `r06e`)
 #pragma unroll
             for (int i = 0; i < IPT; i++)
-                if (pw + i * 64 < m) s[rk[i]] = x[i];
+                if (live(i, cp)) s[rk[i]] = x[i];
             __syncthreads();
             if (p + 1 < np) {
 #pragma unroll
@@ -377,6 +413,7 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
         const uint32_t bw = two ? bw_two : (rest - at + (np - p) - 1) / (np - p);
         const uint32_t sh = Q + at, dm = (1u << bw) - 1;
         at += bw;
+        const bool cp = COMPACT && early && p + 1 == np;  // (block-uniform)
         // (two: the second pass's per-wave counters, 2^(bw - 1) <= 512 words)
         const uint32_t nwd = two ? 1u << (bw - 1) : (uint32_t)FWORD;
         if (TWO_OK && two) {
@@ -389,7 +426,7 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
         uint32_t rk[IPT];
 #pragma unroll
         for (int i = 0; i < IPT; i++) {
-            const bool valid = pw + i * 64 < m;
+            const bool valid = live(i, cp);
             const uint32_t d = (uint32_t)(x[i] >> sh) & dm;
             const uint32_t hs = (d & 1u) * 16u;
             if (PIPE) {
@@ -453,7 +490,7 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
             }
 #pragma unroll
             for (int i = 0; i < IPT; i++)
-                if (pw + i * 64 < m) s[rk[i]] = x[i];
+                if (live(i, cp)) s[rk[i]] = x[i];
         } else {
 #pragma unroll
             for (int i0 = 0; i0 < IPT; i0 += 4) {
@@ -465,10 +502,12 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
                 }
 #pragma unroll
                 for (int i = i0; i < i0 + 4 && i < IPT; i++)
-                    if (pw + i * 64 < m) s[sl[i - i0]] = x[i];
+                    if (live(i, cp)) s[sl[i - i0]] = x[i];
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
+        // (after the scatter here: ahead of it the 80-VGPR instance spills)
+        if (cp) compact_lookback();
         __syncthreads();
         if (p + 1 < np) {
 #pragma unroll
@@ -485,68 +524,16 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
     }
 
     RSTAMP(r, 2);
+    // the compacting last pass ran: the rows are in place and counted
+    const bool compacted = COMPACT && early;  // (block-uniform)
     // ---- run-length pass (thread t: sorted positions t*IPT ..)
     const uint32_t q0 = (uint32_t)t * IPT;
-    uint32_t heads = 0, tails = 0;
+    uint32_t heads = 0, tails = 0, emit = 0, lh_before = 0, off = 0;
+    // (compacted: etot, the same in every thread -- block_exclusive_scan1
+    // hands each thread the sum of all the waves' totals)
+    uint32_t total = etot;
 #define RKEY(v) (((v) >> Q) & rmask)
     T kv[IPT];
-#pragma unroll
-    for (int j = 0; j < IPT; j++) kv[j] = q0 + j < m ? s[q0 + j] : 0;
-    if (early) {
-        // the early count's marks are the rows (heads & tails below)
-        uint32_t marks = 0;
-#pragma unroll
-        for (int j = 0; j < IPT; j++) marks |= (uint32_t)(q0 + j < m && ((uint64_t)kv[j] & MARK)) << j;
-        heads = tails = marks;
-        if (CHK) {
-            // the rows the sorted keys give: a singleton differs from both
-            // neighbours in its whole rest
-            uint32_t single = 0;
-            const uint64_t kl = q0 > 0 && q0 - 1 < m ? RKEY((uint64_t)s[q0 - 1]) : ~0ull;
-            const uint64_t kr = q0 + IPT < m ? RKEY((uint64_t)s[q0 + IPT]) : ~0ull;
-#pragma unroll
-            for (int j = 0; j < IPT; j++) {
-                const uint32_t q = q0 + j;
-                const uint64_t kq = RKEY((uint64_t)kv[j]);
-                const bool h = q == 0 || kq != (j ? RKEY((uint64_t)kv[j - 1]) : kl);
-                const bool e = q + 1 == m || kq != (j + 1 < IPT ? RKEY((uint64_t)kv[j + 1]) : kr);
-                single |= (uint32_t)(q < m && h && e) << j;
-            }
-            if (single != marks) atomicOr(err, ERR_EARLY);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < IPT; j++) {
-            const uint32_t q = q0 + j;
-            if (q < m) {
-                const uint64_t kq = RKEY(kv[j]);
-                const bool h = q == 0 || kq != RKEY(j ? kv[j - 1] : s[q - 1]);
-                const bool e = q + 1 == m || kq != RKEY(j + 1 < IPT ? kv[j + 1] : s[q + 1]);
-                heads |= (uint32_t)h << j;
-                tails |= (uint32_t)e << j;
-            }
-        }
-    }
-    uint32_t emit = 0, lh_before = 0;
-    if constexpr (MODE == RG_UNIQ) {
-        emit = heads & tails;
-    } else {
-        emit = tails;
-        const uint32_t lh = heads ? q0 + (31 - __clz(heads)) + 1 : 0u;
-        lh_before = block_exclusive_scan1<NT>(
-            lh, [](uint32_t a, uint32_t b) { return a > b ? a : b; }, 0u, lds_scan2, (uint32_t *)nullptr);
-    }
-    const uint32_t ne = (uint32_t)__popc(emit);
-    uint32_t total;
-    // (its barrier orders every read of s above before the staging writes below)
-    const uint32_t off = block_exclusive_scan1<NT>(ne, SumU32(), 0u, lds_scan, &total);
-    if (early && t == 0 && total != etot) atomicOr(err, ERR_EARLY);  // (the published count is not the rows')
-    RSTAMP(r, 3);
-    if (w == 0) {
-        const uint64_t ob = early ? wave_lookback_published<0>(status, r, total, epoch, err)
-                                  : wave_lookback<0>(status, r, total, epoch, err);
-        if (lane == 0) s_out = ob;
-    }
     // the emitted rows compacted in LDS as one word each: the item itself
     // (UNIQ: key rest + pos) or key rest | group size << rest (COUNT); every
     // read of s above came before the scan's barriers.  NARROW: the key
@@ -565,8 +552,71 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
             }
         }
     };
-    stage(false);
-    __syncthreads();
+    if (!compacted) {
+#pragma unroll
+        for (int j = 0; j < IPT; j++) kv[j] = q0 + j < m ? s[q0 + j] : 0;
+        // (a COMPACT instance comes here without the early count only)
+        if (!COMPACT && early) {
+            // the early count's marks are the rows (heads & tails below)
+            uint32_t marks = 0;
+#pragma unroll
+            for (int j = 0; j < IPT; j++) marks |= (uint32_t)(q0 + j < m && ((uint64_t)kv[j] & MARK)) << j;
+            heads = tails = marks;
+            if (CHK) {
+                // the rows the sorted keys give: a singleton differs from both
+                // neighbours in its whole rest
+                uint32_t single = 0;
+                const uint64_t kl = q0 > 0 && q0 - 1 < m ? RKEY((uint64_t)s[q0 - 1]) : ~0ull;
+                const uint64_t kr = q0 + IPT < m ? RKEY((uint64_t)s[q0 + IPT]) : ~0ull;
+#pragma unroll
+                for (int j = 0; j < IPT; j++) {
+                    const uint32_t q = q0 + j;
+                    const uint64_t kq = RKEY((uint64_t)kv[j]);
+                    const bool h = q == 0 || kq != (j ? RKEY((uint64_t)kv[j - 1]) : kl);
+                    const bool e = q + 1 == m || kq != (j + 1 < IPT ? RKEY((uint64_t)kv[j + 1]) : kr);
+                    single |= (uint32_t)(q < m && h && e) << j;
+                }
+                if (single != marks) atomicOr(err, ERR_EARLY);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < IPT; j++) {
+                const uint32_t q = q0 + j;
+                if (q < m) {
+                    const uint64_t kq = RKEY(kv[j]);
+                    const bool h = q == 0 || kq != RKEY(j ? kv[j - 1] : s[q - 1]);
+                    const bool e = q + 1 == m || kq != RKEY(j + 1 < IPT ? kv[j + 1] : s[q + 1]);
+                    heads |= (uint32_t)h << j;
+                    tails |= (uint32_t)e << j;
+                }
+            }
+        }
+        if constexpr (MODE == RG_UNIQ) {
+            emit = heads & tails;
+        } else {
+            emit = tails;
+            const uint32_t lh = heads ? q0 + (31 - __clz(heads)) + 1 : 0u;
+            lh_before = block_exclusive_scan1<NT>(
+                lh, [](uint32_t a, uint32_t b) { return a > b ? a : b; }, 0u, lds_scan2, (uint32_t *)nullptr);
+        }
+        const uint32_t ne = (uint32_t)__popc(emit);
+        // (its barrier orders every read of s above before the staging writes below)
+        off = block_exclusive_scan1<NT>(ne, SumU32(), 0u, lds_scan, &total);
+        // ERR_EARLY, the published count is not the rows': raised by the
+        // checked instances only -- a COMPACT instance has no second count to
+        // compare with, its rows ARE the marked items (total = etot above)
+        if (!COMPACT && early && t == 0 && total != etot) atomicOr(err, ERR_EARLY);
+        RSTAMP(r, 3);
+        if (w == 0) {
+            const uint64_t ob = !COMPACT && early ? wave_lookback_published<0>(status, r, total, epoch, err)
+                                                  : wave_lookback<0>(status, r, total, epoch, err);
+            if (lane == 0) s_out = ob;
+        }
+        stage(false);
+        __syncthreads();
+    } else {
+        RSTAMP(r, 3);
+    }
     RSTAMP(r, 4);
     if (NARROW) __builtin_amdgcn_s_setprio(2);  // (the row stores)
     const uint64_t ob = s_out;
@@ -598,15 +648,10 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
             }
         }
     };
-    each_row([&](uint32_t q, uint64_t v) {
+    auto put_key = [&](uint32_t q, uint64_t v) {
         __builtin_nontemporal_store(((uint64_t)(r + rbase) << rest) | RKEY(v), okeys + ob + q);
-    });
-    if constexpr (NARROW) {
-        __syncthreads();  // (every key read before the sizes overwrite them)
-        stage(true);
-        __syncthreads();
-    }
-    each_row([&](uint32_t q, uint64_t v) {
+    };
+    auto put_val = [&](uint32_t q, uint64_t v) {
         if constexpr (MODE == RG_UNIQ) {
             const uint64_t idx = v & qmask;
             const uint64_t pos = rc ? idx : (idx << 1);
@@ -619,7 +664,24 @@ __global__ __launch_bounds__(FT, (fin_waves<T, ATOMIC, CAP>())) void rg_finish(
         } else {
             __builtin_nontemporal_store((O)(v >> rest), ovals + ob + q);
         }
-    });
+    };
+    if constexpr (MODE == RG_UNIQ && CHK == 0) {
+        // a uniq row is read once for its key and its pos: global row ob + q
+        // of lane 0 is a multiple of 64 in both streams, so the 4- or 8-byte
+        // pos stores of a wave cover whole lines as the key stores do
+        each_row([&](uint32_t q, uint64_t v) {
+            put_key(q, v);
+            put_val(q, v);
+        });
+    } else {
+        each_row(put_key);
+        if constexpr (NARROW) {
+            __syncthreads();  // (every key read before the sizes overwrite them)
+            stage(true);
+            __syncthreads();
+        }
+        each_row(put_val);
+    }
 #undef RKEY
     RSTAMP(r, 5);
 }
