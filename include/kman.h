@@ -188,6 +188,23 @@ int kman_parse_fasta_at(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, 
  * info is zeroed then.  Launches are timed under the tag "parse_fastq". */
 int kman_parse_fastq(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_codes,
                      uint64_t *d_rec_hdr, uint64_t *d_rec_seq, uint64_t rec_cap, kman_parse_info *info);
+/* kman_parse_fastq with a quality threshold.  min_qual_byte is the threshold
+ * byte T = phred offset + minimal quality, 0..255 (KMAN_EINVAL above); 0 is
+ * kman_parse_fastq itself (the same launches).  A kept sequence byte (one that
+ * has a code) at column c of its raw line 4r + 1 is masked when the byte at
+ * column c of line 4r + 3 is < T, compared unsigned; columns are counted on
+ * the raw lines, before cleaning (blanks inside a sequence line shift code
+ * indices, not columns).  A masked code becomes 4 | (code & 8): the code of an
+ * 'N' at that place, bit 3 kept.  Everything else (n_bases, n_records, the
+ * record table, the 64 pad bytes, every error) is as without a threshold: the
+ * outputs are those of kman_parse_fasta for the FASTA of the same records with
+ * every masked byte replaced by 'N'.  The mask pass runs after the validation
+ * has passed, and is timed under "parse_fastq" too.  *n_masked (may be NULL):
+ * the kept bytes whose quality byte is < T, already not-ACGT ones included; 0
+ * on error. */
+int kman_parse_fastq_q(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_codes,
+                       uint64_t *d_rec_hdr, uint64_t *d_rec_seq, uint64_t rec_cap,
+                       kman_parse_info *info, uint32_t min_qual_byte, uint64_t *n_masked);
 
 /* Number of k-mers kman_extract will emit (valid windows x (RC ? 2 : 1)). */
 int kman_count_kmers(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases, uint32_t k,

@@ -89,6 +89,11 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, POINTER(ParseInfo)],
     ),
+    "kman_parse_fastq_q": (
+        c_int,
+        [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, POINTER(ParseInfo), c_uint32,
+         POINTER(c_uint64)],
+    ),
     "kman_count_kmers": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, POINTER(c_uint64)]),
     "kman_extract": (
         c_int,

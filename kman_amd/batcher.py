@@ -150,11 +150,15 @@ class FastaBatcher(BatcherThreading):
     def __init__(self, scan_mode: "FastaBatcher.MODE" = MODE.KMERS, reverse: bool = False, threads: int = 1,
                  size: int = BatcherThreading.DEFAULT_BATCH_SIZE, natype: NATYPES = BatcherThreading.DEFAULT_NATYPE,
                  tmp: Optional[str] = None, device: Optional[engine.Device] = None,
-                 distributed: Optional[bool] = None, fmt: str = "auto"):
+                 distributed: Optional[bool] = None, fmt: str = "auto", min_qual: int = 0,
+                 phred_offset: int = 33):
         super().__init__(size, threads, natype, tmp if tmp is not None else tempfile.gettempdir())
         if fmt not in engine.FORMATS:
             raise AssertionError("format must be one of %s, got %r" % (", ".join(engine.FORMATS), fmt))
         self.fmt = fmt  # input format: "auto" (engine.sniff_format), "fasta" or "fastq"
+        # FASTQ quality threshold (engine.parse_fastq): bases below it read as N; 0 = none
+        self._qbyte = engine._qual_byte(min_qual, phred_offset)
+        self.min_qual, self.phred_offset = min_qual, phred_offset
         self.mode = scan_mode
         self.doReverseComplement = reverse
         self._device = device
@@ -195,9 +199,10 @@ class FastaBatcher(BatcherThreading):
         from . import launch
         from .source import FastaSource
 
+        fmt = engine.sniff_file(fasta) if self.fmt == "auto" else self.fmt
+        engine._check_qual_format(self._qbyte, fmt)  # (before any device work)
         dev = self._device or engine.default_device()
         dist = launch.distributed() if self._distributed is None else self._distributed
-        fmt = engine.sniff_file(fasta) if self.fmt == "auto" else self.fmt
         if dist and k <= engine.MAX_K and fmt != "fastq":  # (the byte-range shards cut FASTA only)
             # this rank's byte range only; ONE batch of its windows, joined
             # across the ranks by KJoiner.join (the batch cut does not change
@@ -207,7 +212,8 @@ class FastaBatcher(BatcherThreading):
             n = src.n_kmers
             self.feed_collection([Batch.from_source(src, 0, n, max(1, n), self.tmp)], feedMode)
             return self
-        src = FastaSource(dev, None, k, self.doReverseComplement, path=fasta, fmt=fmt)
+        src = FastaSource(dev, None, k, self.doReverseComplement, path=fasta, fmt=fmt, min_qual=self.min_qual,
+                          phred_offset=self.phred_offset)
         self.source = src
         if fmt == "fastq":  # (reads: millions of records, one line for all)
             logging.info("Batching %d reads..." % src.parsed.n_records)

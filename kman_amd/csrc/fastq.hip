@@ -26,6 +26,11 @@
 // Memory traffic: the text is read twice, about half of it is written as
 // codes, 8 B per line and 16 B per record of tables: ~2.7 B per input byte for
 // 150-base reads.
+//
+// A quality threshold (kman_parse_fastq_q) adds one pass, fq_qmask, after the
+// validation: a kept sequence byte whose quality byte (same column, two lines
+// on) is below the threshold has its code turned into that of an 'N'.  See the
+// kernel for its traffic.
 #include "common.h"
 
 namespace {
@@ -86,6 +91,12 @@ KMAN_DEV uint32_t eq_bytes(uint32_t w, uint32_t c) { return zero_bytes(w ^ (c * 
 // bytes below c (c <= 0x80)
 KMAN_DEV uint32_t lt_bytes(uint32_t w, uint32_t c) {
     return ~((w & 0x7f7f7f7fu) + (0x80u - c) * 0x01010101u) & ~w & 0x80808080u;
+}
+// bytes below c, unsigned, for any c in 1..255
+KMAN_DEV uint32_t lt_bytes_u8(uint32_t w, uint32_t c) {
+    const bool hi = c > 0x80u;  // (then every byte below 0x80 passes, the others by their low 7 bits)
+    const uint32_t lo7 = ~((w & 0x7f7f7f7fu) + (0x80u - (hi ? c - 0x80u : c)) * 0x01010101u) & 0x80808080u;
+    return hi ? ((~w & 0x80808080u) | (lo7 & w)) : (lo7 & ~w);
 }
 // the 0x80 bits of four bytes -> a 4-bit mask
 KMAN_DEV uint32_t hibits4(uint32_t m) {
@@ -469,13 +480,146 @@ __global__ void fq_report(const uint8_t *__restrict__ text, uint64_t n, const ui
     info[FI_LEN_QUAL] = lq;
 }
 
-}  // namespace
 
-extern "C" int kman_parse_fastq(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_codes,
-                                uint64_t *d_rec_hdr, uint64_t *d_rec_seq, uint64_t rec_cap,
-                                kman_parse_info *info) {
+// ---------------------------------------------------------------- quality mask
+// bits of the tile's codes [0, al + tile_kept), al <= 15, in 32-bit words
+constexpr int QBM_WORDS = (PTILE + 16 + 31) / 32 + 3;
+
+// the four text bytes at `off` (off % 4 == 0; the text is 16-byte aligned),
+// zeros past the end of the text
+KMAN_DEV uint32_t text_word(const uint8_t *text, uint64_t n, uint64_t off) {
+    if (off + 4 <= n) return *reinterpret_cast<const uint32_t *>(text + off);
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++) v |= (off + b < n ? (uint32_t)text[off + b] : 0u) << (8 * b);
+    return v;
+}
+// codes of four bases, those picked by the 4-bit mask x turned into an N's
+// (4, bit 3 kept)
+KMAN_DEV uint32_t mask_codes4(uint32_t c, uint32_t x) {
+    const uint32_t mm = ((x * 0x00204081u) & 0x01010101u) * 0xffu;
+    return (c & ~mm) | (((c & 0x08080808u) | 0x04040404u) & mm);
+}
+
+// The codes of the kept sequence bytes whose quality byte is below T become
+// 4 | (code & 8).  fq_emit's geometry and prefixes give every chunk its
+// sequence-byte mask, the index of its first code and the line of each run of
+// sequence bytes; the quality bytes of a run sit lstart[g + 2] - lstart[g]
+// further on.  The low-quality bits of a chunk, compacted to its codes, are
+// OR-ed into a bit map of the tile's codes in LDS (2 KiB; three LDS atomics
+// per chunk at most); then the tile's codes are rewritten as 16-byte vectors
+// at their own alignment, skipping the vectors without a masked code, the two
+// end vectors shared with the neighbour tiles bytewise.  Runs after
+// fq_validate has passed, so line g + 2 exists and is as long as line g.
+__global__ __launch_bounds__(PT) void fq_qmask(const uint8_t *__restrict__ text, uint64_t n,
+                                               const Lq64 *__restrict__ local, const Lq64 *__restrict__ bpre,
+                                               const uint64_t *__restrict__ lstart, uint64_t n_eff, uint32_t T,
+                                               uint8_t *__restrict__ codes,
+                                               unsigned long long *__restrict__ n_masked) {
+    __shared__ Lq lds[PT / 64];
+    __shared__ uint32_t cnt_lds[PT / 64];
+    __shared__ uint32_t bm[QBM_WORDS];
+    for (uint32_t i = threadIdx.x; i < (uint32_t)QBM_WORDS; i += PT) bm[i] = 0;  // (the scan's barriers order this)
+    const uint32_t tb = blockIdx.x;
+    const uint64_t pos = (uint64_t)tb * PTILE + (uint64_t)threadIdx.x * PB;
+    Chunk ch;
+    load_chunk(text, n, pos, ch);
+    uint64_t em;   // this chunk's bytes of sequence lines
+    uint64_t L0;   // lines started before this chunk
+    uint32_t lk0, tile_kept;
+    uint64_t tile_base;
+    {
+        uint64_t km[4];
+        residue_masks(ch, km);
+        const Lq x = chunk_lq(ch, km);
+        Lq tot;
+        const Lq pre = block_exclusive_scan<PT>(x, ComposeLq<Lq>(), lq_id<Lq>(), lds, &tot);
+        const Lq64 p = ComposeLq<Lq64>()(bpre[tb / SCAN_T], local[tb]);
+        tile_base = p.k[2];
+        const uint32_t rt = (2u - (uint32_t)p.lines) & 3u;
+        lk0 = sel4(pre.k, rt);
+        tile_kept = sel4(tot.k, rt);
+        em = sel4(km, (rt - pre.lines) & 3u);
+        L0 = p.lines + pre.lines;
+    }
+    const uint32_t al = (uint32_t)(tile_base & 15u);
+    uint32_t nm = 0;
+    if (em) {
+        uint64_t mc = 0;  // bit o: the chunk's o-th code is masked
+        const int a = __ffsll((unsigned long long)em) - 1;
+        const uint64_t run = em >> a;
+        if ((run & (run + 1)) == 0) {
+            // one run [a, a + cnt): its line is the one byte a lies in
+            const uint64_t g = L0 + (uint64_t)__popcll(ch.ls & bits_below(a + 1)) - 1;
+            if (g + 2 <= n_eff) {
+                // the 64 bytes at pos + delta, unaligned: 17 dwords, byte-aligned in pairs
+                const uint64_t qpos = pos + (lstart[g + 2] - lstart[g]);
+                const uint64_t off0 = qpos & ~3ull;
+                const uint32_t sh = (uint32_t)(qpos & 3u);
+                uint32_t d[PB / 4 + 1];
+#pragma unroll
+                for (int j = 0; j <= PB / 4; j++) d[j] = text_word(text, n, off0 + 4 * (uint64_t)j);
+                uint64_t low = 0;
+#pragma unroll
+                for (int v = 0; v < PB / 4; v++) {
+                    const uint32_t qw = __builtin_amdgcn_alignbyte(d[v + 1], d[v], sh);
+                    low |= (uint64_t)hibits4(lt_bytes_u8(qw, T)) << (4 * v);
+                }
+                mc = (em & low) >> a;
+            }
+        } else {
+            // several runs in one chunk (short lines, or blanks inside a line)
+            uint32_t o = 0;
+            for (uint64_t m = em; m; m &= m - 1, o++) {
+                const int i = __ffsll((unsigned long long)m) - 1;
+                const uint64_t g = L0 + (uint64_t)__popcll(ch.ls & bits_below(i + 1)) - 1;
+                if (g + 2 > n_eff) continue;
+                const uint64_t qp = pos + (uint64_t)i + (lstart[g + 2] - lstart[g]);
+                if (qp < n && (uint32_t)text[qp] < T) mc |= 1ull << o;
+            }
+        }
+        nm = (uint32_t)__popcll(mc);
+        if (mc) {
+            const uint32_t lk = al + lk0, w0 = lk >> 5, s = lk & 31u;
+            const uint64_t lo = mc << s;
+            const uint32_t x0 = (uint32_t)lo, x1 = (uint32_t)(lo >> 32), x2 = s ? (uint32_t)(mc >> (64 - s)) : 0u;
+            if (x0) atomicOr(&bm[w0], x0);
+            if (x1) atomicOr(&bm[w0 + 1], x1);
+            if (x2) atomicOr(&bm[w0 + 2], x2);
+        }
+    }
+    uint32_t nm_tile;
+    (void)block_exclusive_scan<PT>(nm, SumU32(), 0u, cnt_lds, &nm_tile);  // (its barriers publish bm)
+    if (nm_tile == 0) return;
+    if (threadIdx.x == 0) atomicAdd(n_masked, (unsigned long long)nm_tile);
+    uint8_t *dst = codes + (tile_base - al);
+    const uint32_t end = al + tile_kept;
+    const uint32_t nwords = (end + 15) / 16;
+    for (uint32_t q = threadIdx.x; q < nwords; q += PT) {
+        const uint32_t bits = (bm[q >> 1] >> (16 * (q & 1u))) & 0xffffu;
+        if (!bits) continue;
+        const uint32_t b0 = q * 16;
+        if (b0 >= al && b0 + 16 <= end) {
+            uint4 c = *reinterpret_cast<const uint4 *>(dst + b0);
+            c.x = mask_codes4(c.x, bits & 15u);
+            c.y = mask_codes4(c.y, (bits >> 4) & 15u);
+            c.z = mask_codes4(c.z, (bits >> 8) & 15u);
+            c.w = mask_codes4(c.w, bits >> 12);
+            *reinterpret_cast<uint4 *>(dst + b0) = c;
+        } else {
+            for (uint32_t b = 0; b < 16; b++)  // (bits are set inside [al, end) only)
+                if ((bits >> b) & 1u) dst[b0 + b] = (uint8_t)(4u | (dst[b0 + b] & 8u));
+        }
+    }
+}
+
+// qbyte: the quality threshold byte (0: no mask pass); n_masked may be null
+int parse_fastq(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_codes, uint64_t *d_rec_hdr,
+                uint64_t *d_rec_seq, uint64_t rec_cap, kman_parse_info *info, uint32_t qbyte, uint64_t *n_masked) {
     if (!ctx || !info) return KMAN_EINVAL;
     info->n_bases = info->n_records = 0;
+    if (n_masked) *n_masked = 0;
+    if (qbyte > 255) return kman_fail(ctx, KMAN_EINVAL, "quality threshold byte %u > 255", qbyte);
     if (n_bytes && (!d_text || !d_codes)) return kman_fail(ctx, KMAN_EINVAL, "null buffer");
     if (((uintptr_t)d_text & 15) != 0) return kman_fail(ctx, KMAN_EINVAL, "text must be 16-byte aligned");
     if (((uintptr_t)d_codes & 15) != 0) return kman_fail(ctx, KMAN_EINVAL, "codes must be 16-byte aligned");
@@ -539,7 +683,33 @@ extern "C" int kman_parse_fastq(kman_ctx *ctx, const uint8_t *d_text, uint64_t n
                              (unsigned long long)ctx->h_small[FI_LEN_SEQ]);
         }
     }
+    if (qbyte) {
+        // the tile prefixes are still in the scratch, the line starts in aux
+        unsigned long long *d_nm = (unsigned long long *)(d_info + FI_WORDS + 2);
+        HIP_TRY(ctx, hipMemsetAsync(d_nm, 0, sizeof(*d_nm), ctx->stream));
+        { KTimer kt_(ctx, "parse_fastq");
+        hipLaunchKernelGGL(fq_qmask, dim3((uint32_t)T), dim3(PT), 0, ctx->stream, d_text, n_bytes, d_local, d_bpre,
+                           d_lstart, n_eff, qbyte, d_codes, d_nm); }
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small, d_nm, sizeof(*d_nm), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (n_masked) *n_masked = ctx->h_small[0];
+    }
     info->n_bases = n_bases;
     info->n_records = R;
     return KMAN_OK;
+}
+
+}  // namespace
+
+extern "C" int kman_parse_fastq(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_codes,
+                                uint64_t *d_rec_hdr, uint64_t *d_rec_seq, uint64_t rec_cap,
+                                kman_parse_info *info) {
+    return parse_fastq(ctx, d_text, n_bytes, d_codes, d_rec_hdr, d_rec_seq, rec_cap, info, 0, nullptr);
+}
+
+extern "C" int kman_parse_fastq_q(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_codes,
+                                  uint64_t *d_rec_hdr, uint64_t *d_rec_seq, uint64_t rec_cap,
+                                  kman_parse_info *info, uint32_t min_qual_byte, uint64_t *n_masked) {
+    return parse_fastq(ctx, d_text, n_bytes, d_codes, d_rec_hdr, d_rec_seq, rec_cap, info, min_qual_byte, n_masked);
 }

@@ -11,6 +11,7 @@ engine function        reference                                   kernel(s)
 =====================  ==========================================  ============================
 ``parse``              SmartFastaParser.parse, parsers.py:86-128   parse_reduce/scan/emit
 ``parse_fastq``        (four-line FASTQ; not in the reference)     fq_reduce/scan/emit/validate
+``  min_qual > 0``     (quality threshold: low bases read as N)    + fq_qmask
 ``record names``       record[0].split(" ")[0], batcher.py:551     host (names only)
 ``extract``            Sequence.yield_kmers, seq.py:285-328        extract_kernel
 ``sort``               Batch.sorted, batch.py:156-168              onesweep_pass x P
@@ -23,6 +24,7 @@ engine function        reference                                   kernel(s)
 from __future__ import annotations
 
 import ctypes
+import logging
 import os
 from collections.abc import Sequence as _SequenceABC
 from ctypes import byref, c_int, c_size_t, c_uint32, c_uint64, c_void_p
@@ -197,6 +199,7 @@ class Parsed:
     names: List[bytes]
     names_blob: bytes
     name_off: np.ndarray  # u64, len n_records + 1
+    n_masked: int = 0  # FASTQ with a quality threshold: the kept bytes below it (their codes read as N)
 
     def record_of(self, base: int) -> int:
         return int(np.searchsorted(self.rec_seq, base, side="right")) - 1
@@ -206,6 +209,23 @@ class Parsed:
 
 
 FORMATS = ("auto", "fasta", "fastq")
+MAX_MIN_QUAL = 93  # '~' at offset 33
+PHRED_OFFSETS = (33, 64)
+
+
+def _qual_byte(min_qual: int, phred_offset: int) -> int:
+    """The threshold byte of kman_parse_fastq_q, `phred_offset` + `min_qual`
+    (0 for ``min_qual == 0``: no threshold), both checked."""
+    if isinstance(min_qual, bool) or not isinstance(min_qual, (int, np.integer)) or not 0 <= min_qual <= MAX_MIN_QUAL:
+        raise AssertionError("min_qual must be an integer in 0..%d, got %r" % (MAX_MIN_QUAL, min_qual))
+    if isinstance(phred_offset, bool) or phred_offset not in PHRED_OFFSETS:
+        raise AssertionError("phred_offset must be 33 or 64, got %r" % (phred_offset,))
+    return int(phred_offset) + int(min_qual) if min_qual else 0
+
+
+def _check_qual_format(qbyte: int, fmt: str) -> None:
+    if qbyte and fmt != "fastq":
+        raise AssertionError("--min-qual needs fastq input")
 
 
 def sniff_format(head: bytes) -> str:
@@ -348,16 +368,37 @@ def fastq_names(text, rec_hdr: np.ndarray) -> Tuple[bytes, np.ndarray]:
     return b"".join(pieces), name_off
 
 
-def _parsed_fastq(dev: Device, codes: DeviceBuffer, info, rec_hdr, rec_seq, text) -> Parsed:
+def _parsed_fastq(dev: Device, codes: DeviceBuffer, info, rec_hdr, rec_seq, text, n_masked: int = 0,
+                  min_qual: int = 0) -> Parsed:
     blob, name_off = fastq_names(text, rec_hdr)
+    if min_qual:
+        logging.info("masked %d of %d bases below Q%d" % (n_masked, int(info.n_bases), min_qual))
     return Parsed(dev, codes, int(info.n_bases), int(info.n_records), rec_hdr, rec_seq, BlobNames(blob, name_off),
-                  blob, name_off)
+                  blob, name_off, n_masked)
 
 
-def parse_fastq(dev: Device, text: bytes) -> Parsed:
+def _call_parse_fastq(dev: Device, d_text, n: int, codes, d_hdr, d_seq, cap: int, info, qbyte: int) -> int:
+    """kman_parse_fastq, or kman_parse_fastq_q under a threshold byte; returns n_masked."""
+    L = N.lib()
+    if not qbyte:
+        N.check(dev.ctx, L.kman_parse_fastq(dev.ctx, c_void_p(d_text.ptr), n, c_void_p(codes.ptr), c_void_p(d_hdr.ptr),
+                                            c_void_p(d_seq.ptr), cap, byref(info)), "kman_parse_fastq")
+        return 0
+    masked = ctypes.c_uint64(0)
+    N.check(dev.ctx, L.kman_parse_fastq_q(dev.ctx, c_void_p(d_text.ptr), n, c_void_p(codes.ptr), c_void_p(d_hdr.ptr),
+                                          c_void_p(d_seq.ptr), cap, byref(info), qbyte, byref(masked)),
+            "kman_parse_fastq_q")
+    return int(masked.value)
+
+
+def parse_fastq(dev: Device, text: bytes, min_qual: int = 0, phred_offset: int = 33) -> Parsed:
     """Four-line FASTQ bytes -> device codes + record table (kman_parse_fastq):
     the same ``Parsed`` as ``parse`` gives for the FASTA of the same records;
-    the names follow the record name rule applied to the ``@`` line."""
+    the names follow the record name rule applied to the ``@`` line.  With
+    `min_qual` > 0 (0..93) every base whose quality byte is below
+    `phred_offset` (33 or 64) + `min_qual` reads as ``N`` (kman_parse_fastq_q);
+    ``Parsed.n_masked`` counts them."""
+    qbyte = _qual_byte(min_qual, phred_offset)
     n = len(text)
     if n == 0:
         raise AssertionError("premature end of file or empty file")
@@ -373,9 +414,7 @@ def parse_fastq(dev: Device, text: bytes) -> Parsed:
         d_seq = dev.alloc(8 * cap)
         try:
             info = N.ParseInfo()
-            rc = L.kman_parse_fastq(dev.ctx, c_void_p(d_text.ptr), n, c_void_p(codes.ptr), c_void_p(d_hdr.ptr),
-                                    c_void_p(d_seq.ptr), cap, byref(info))
-            N.check(dev.ctx, rc, "kman_parse_fastq")
+            n_masked = _call_parse_fastq(dev, d_text, n, codes, d_hdr, d_seq, cap, info, qbyte)
             R = int(info.n_records)
             rec_hdr = dev.download(d_hdr, R, np.uint64)
             rec_seq = dev.download(d_seq, R, np.uint64)
@@ -387,16 +426,20 @@ def parse_fastq(dev: Device, text: bytes) -> Parsed:
         raise
     finally:
         d_text.free()
-    p = _parsed_fastq(dev, codes, info, rec_hdr, rec_seq, text)
+    p = _parsed_fastq(dev, codes, info, rec_hdr, rec_seq, text, n_masked, min_qual)
     phases.mark("parse")
     return p
 
 
-def parse(dev: Device, text: bytes, fmt: str = "auto") -> Parsed:
+def parse(dev: Device, text: bytes, fmt: str = "auto", min_qual: int = 0, phred_offset: int = 33) -> Parsed:
     """FASTA bytes -> device codes + record table (kman_parse_fasta); FASTQ
-    bytes (`fmt`, ``auto``: sniff_format) go to parse_fastq."""
-    if _resolve_format(fmt, lambda at: bytes(text[at:at + (1 << 16)])) == "fastq":
-        return parse_fastq(dev, text)
+    bytes (`fmt`, ``auto``: sniff_format) go to parse_fastq, with its quality
+    threshold (`min_qual` > 0 needs FASTQ input)."""
+    qbyte = _qual_byte(min_qual, phred_offset)
+    fmt = _resolve_format(fmt, lambda at: bytes(text[at:at + (1 << 16)]))
+    _check_qual_format(qbyte, fmt)
+    if fmt == "fastq":
+        return parse_fastq(dev, text, min_qual, phred_offset)
     n = len(text)
     if n == 0:
         raise AssertionError("premature end of file or empty file")
@@ -429,16 +472,20 @@ def parse(dev: Device, text: bytes, fmt: str = "auto") -> Parsed:
     return Parsed(dev, codes, int(info.n_bases), R, rec_hdr, rec_seq, names, b"".join(names), name_off)
 
 
-def parse_file(dev: Device, path: str, fmt: str = "auto") -> Parsed:
+def parse_file(dev: Device, path: str, fmt: str = "auto", min_qual: int = 0, phred_offset: int = 33) -> Parsed:
     """kman_parse_fasta of a FASTA file (batcher.py:480 reads it whole), or
     kman_parse_fastq of a FASTQ file (`fmt`, ``auto``: sniff_format).  A
     plain file is read in _FMT_SLICE chunks straight into two pinned stages,
     each chunk's H2D (on the copy stream) running while the next chunk is
     read, so the text crosses host memory once and no pageable copy is made;
     the record names come from the file's header lines (mmap).  Gzip input
-    is inflated into memory and parsed from there (read_input + parse)."""
+    is inflated into memory and parsed from there (read_input + parse).
+    `min_qual`, `phred_offset`: parse_fastq's quality threshold."""
+    qbyte = _qual_byte(min_qual, phred_offset)
     if path.endswith(".gz"):
-        return parse(dev, read_input(path), fmt)
+        if qbyte and fmt != "fastq":  # (decided from the head, before the whole file is inflated)
+            _check_qual_format(qbyte, sniff_file(path) if fmt == "auto" else _resolve_format(fmt, b""))
+        return parse(dev, read_input(path), fmt, min_qual, phred_offset)
     import mmap
 
     L = N.lib()
@@ -447,6 +494,7 @@ def parse_file(dev: Device, path: str, fmt: str = "auto") -> Parsed:
         if n == 0:
             raise AssertionError("premature end of file or empty file")
         fq = _resolve_format(fmt, lambda at: os.pread(fh.fileno(), 1 << 16, at)) == "fastq"
+        _check_qual_format(qbyte, "fastq" if fq else "fasta")
         d_text = dev.alloc(n + 64)
         codes = dev.alloc(n + 64)
         try:
@@ -475,9 +523,13 @@ def parse_file(dev: Device, path: str, fmt: str = "auto") -> Parsed:
             d_seq = dev.alloc(8 * cap)
             try:
                 info = N.ParseInfo()
-                fn, what = (L.kman_parse_fastq, "kman_parse_fastq") if fq else (L.kman_parse_fasta, "kman_parse_fasta")
-                N.check(dev.ctx, fn(dev.ctx, c_void_p(d_text.ptr), n, c_void_p(codes.ptr), c_void_p(d_hdr.ptr),
-                                    c_void_p(d_seq.ptr), cap, byref(info)), what)
+                n_masked = 0
+                if fq:
+                    n_masked = _call_parse_fastq(dev, d_text, n, codes, d_hdr, d_seq, cap, info, qbyte)
+                else:
+                    N.check(dev.ctx, L.kman_parse_fasta(dev.ctx, c_void_p(d_text.ptr), n, c_void_p(codes.ptr),
+                                                        c_void_p(d_hdr.ptr), c_void_p(d_seq.ptr), cap, byref(info)),
+                            "kman_parse_fasta")
                 R = int(info.n_records)
                 rec_hdr = dev.download(d_hdr, R, np.uint64)
                 rec_seq = dev.download(d_seq, R, np.uint64)
@@ -493,7 +545,7 @@ def parse_file(dev: Device, path: str, fmt: str = "auto") -> Parsed:
         try:
             if fq:
                 try:
-                    p = _parsed_fastq(dev, codes, info, rec_hdr, rec_seq, mm)
+                    p = _parsed_fastq(dev, codes, info, rec_hdr, rec_seq, mm, n_masked, min_qual)
                 except BaseException:
                     codes.free()
                     raise
@@ -1353,13 +1405,17 @@ def count_groups(p: Parsed, k: int, rc: bool = False, canonical: bool = False, o
 
 
 def abundance_hist(text: bytes, k: int, canonical: bool = True, nbins: int = 10001,
-                   dev: Optional[Device] = None, fmt: str = "auto") -> np.ndarray:
+                   dev: Optional[Device] = None, fmt: str = "auto", min_qual: int = 0,
+                   phred_offset: int = 33) -> np.ndarray:
     """k-mer abundance spectrum (BASELINE config 5; SURVEY §8f-1, not in the
     reference): h[c] = distinct (canonical) k-mers seen c times, h[-1] every
-    count >= nbins - 1 (kman_count_hist over the count output)."""
-    dev = dev or default_device()
+    count >= nbins - 1 (kman_count_hist over the count output).  `min_qual`,
+    `phred_offset`: parse_fastq's quality threshold."""
     _check_k(k, wide=True)
-    p = parse(dev, text, fmt)
+    _check_qual_format(_qual_byte(min_qual, phred_offset),
+                       _resolve_format(fmt, lambda at: bytes(text[at:at + (1 << 16)])))
+    dev = dev or default_device()
+    p = parse(dev, text, fmt, min_qual, phred_offset)
     try:
         r = count_groups(p, k, False, canonical, ordered=False)
         d_h = dev.alloc(8 * nbins)

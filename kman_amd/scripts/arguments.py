@@ -86,5 +86,16 @@ def input_format():
                                              "with '@', else fasta. Default: auto")
 
 
+def min_qual():
+    return click.option("--min-qual", "-q", "min_qual", type=click.IntRange(0, 93), default=0,
+                        help="fastq INPUT only: bases whose quality is below this Phred score are read as N, "
+                             "so no k-mer spans them. Default: 0 (off)")
+
+
+def phred_offset():
+    return click.option("--phred-offset", "phred_offset", type=click.Choice(["33", "64"]), default="33",
+                        help="ASCII offset of the fastq quality bytes, for --min-qual. Default: 33")
+
+
 def re_sort():
     return click.option("--re-sort", "-R", is_flag=True, help="Force batch re-sorting, when loaded with -B.")

@@ -35,10 +35,11 @@ def main():
     """Entry point."""
 
 
-def _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist=False, fmt="auto"):
+def _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist=False, fmt="auto",
+             min_qual=0, phred_offset=33):
     return (
         FastaBatcher(scan_mode=FastaBatcher.MODE[scan_mode], reverse=reverse, size=batch_size, threads=threads,
-                     tmp=tmp, distributed=dist, fmt=fmt)
+                     tmp=tmp, distributed=dist, fmt=fmt, min_qual=min_qual, phred_offset=phred_offset)
         .do(input_path, k, BatcherThreading.FEED_MODE[batch_mode])
         .collection
     )
@@ -71,11 +72,15 @@ INPUT runs on rank 0 alone).
 @args.tmp()
 @args.re_sort()
 @args.input_format()
+@args.min_qual()
+@args.phred_offset()
 def count(input_path: str, output_path: str, k: int, reverse: bool = False, scan_mode: str = "KMERS",
           batch_size: int = 1000000, batch_mode: str = "APPEND", previous_batches: Optional[str] = None,
           count_mode: str = "SEQ_COUNT", memory_mode: str = "NORMAL", threads: int = 1,
-          tmp: str = tempfile.gettempdir(), re_sort: bool = False, input_format: str = "auto") -> None:
+          tmp: str = tempfile.gettempdir(), re_sort: bool = False, input_format: str = "auto",
+          min_qual: int = 0, phred_offset: str = "33") -> None:
     input_file_exists(input_path)
+    _check_min_qual(min_qual, input_path, input_format, previous_batches)
     set_tempdir(tmp)
     dist = _multi_gpu(k, previous_batches, count_mode, input_path, input_format)
     if dist is None:
@@ -84,10 +89,18 @@ def count(input_path: str, output_path: str, k: int, reverse: bool = False, scan
         batches = load_batches(previous_batches, threads, re_sort)
     else:
         batches = _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist,
-                           input_format)
+                           input_format, min_qual, int(phred_offset))
     prep_joiner(KJoinerThreading(KJoiner.MODE[count_mode], KJoiner.MEMORY[memory_mode]), len(batches),
                 threads).join(batches, output_path)
     logging.info("That's all!")
+
+
+def _check_min_qual(min_qual: int, input_path: str, input_format: str,
+                    previous_batches: Optional[str] = None) -> None:
+    """--min-qual masks bases by the quality line of a fastq INPUT: refused for
+    fasta input and for -B reloads, before any device work or output."""
+    if min_qual > 0 and (previous_batches is not None or not _is_fastq(input_path, input_format)):
+        raise AssertionError("--min-qual needs fastq input")
 
 
 def _is_fastq(input_path: Optional[str], input_format: str) -> bool:
@@ -142,11 +155,14 @@ def prep_joiner(joiner: KJoinerThreading, n_batches: int, threads: int = 1) -> K
 @args.tmp()
 @args.re_sort()
 @args.input_format()
+@args.min_qual()
+@args.phred_offset()
 def uniq(input_path: str, output_path: str, k: int, reverse: bool = False, scan_mode: str = "KMERS",
          batch_size: int = 1000000, batch_mode: str = "APPEND", previous_batches: Optional[str] = None,
          threads: int = 1, tmp: str = tempfile.gettempdir(), re_sort: bool = False,
-         input_format: str = "auto") -> None:
+         input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33") -> None:
     input_file_exists(input_path)
+    _check_min_qual(min_qual, input_path, input_format, previous_batches)
     set_tempdir(tmp)
     dist = _multi_gpu(k, previous_batches, "UNIQUE", input_path, input_format)
     if dist is None:
@@ -155,7 +171,7 @@ def uniq(input_path: str, output_path: str, k: int, reverse: bool = False, scan_
         batches = load_batches(previous_batches, threads, re_sort)
     else:
         batches = _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist,
-                           input_format)
+                           input_format, min_qual, int(phred_offset))
     joiner = KJoinerThreading()
     joiner.threads = threads
     joiner.batch_size = max(2, int(len(batches) / max(1, threads)))
@@ -179,10 +195,14 @@ Batches are written to an OUTPUT folder, which must be empty or non-existent.
 @args.tmp()
 @args.compress()
 @args.input_format()
+@args.min_qual()
+@args.phred_offset()
 def batch(input_path: str, output_path: str, k: int, reverse: bool = False, scan_mode: str = "KMERS",
           batch_size: int = 1000000, batch_mode: str = "APPEND", threads: int = 1,
-          tmp: str = tempfile.gettempdir(), compress: bool = False, input_format: str = "auto") -> None:
+          tmp: str = tempfile.gettempdir(), compress: bool = False, input_format: str = "auto",
+          min_qual: int = 0, phred_offset: str = "33") -> None:
     input_file_exists(input_path)
+    _check_min_qual(min_qual, input_path, input_format)
     if launch.distributed() and not launch.solo_rank():
         launch.log_solo("kmer batch")  # (the batch files are one stream's consecutive chunks)
         return
@@ -192,7 +212,7 @@ def batch(input_path: str, output_path: str, k: int, reverse: bool = False, scan
     os.makedirs(output_path, exist_ok=True)
     try:
         copy_batches(_batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, False,
-                              input_format), output_path, compress)
+                              input_format, min_qual, int(phred_offset)), output_path, compress)
     except IOError as e:
         logging.error(f"Unable to write to output directory '{output_path}'.\n{e}")
     logging.info("That's all!")
@@ -214,9 +234,12 @@ INPUT fasta or fastq file, plain or gzipped.
 @click.option("--max-count", type=click.INT, default=10000, show_default=True,
               help="Abundances from this one up share the last line (>=N).")
 @args.input_format()
+@args.min_qual()
+@args.phred_offset()
 def hist(input_path: str, output_path: str, k: int, forward: bool = False, max_count: int = 10000,
-         input_format: str = "auto") -> None:
+         input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33") -> None:
     input_file_exists(input_path)
+    _check_min_qual(min_qual, input_path, input_format)
     if k <= 1:
         raise AssertionError("k must be >= 1, got %d instead." % k)
     fastq = launch.distributed() and _is_fastq(input_path, input_format)
@@ -240,7 +263,7 @@ def hist(input_path: str, output_path: str, k: int, forward: bool = False, max_c
         logging.info("That's all!")
         return
     h = engine.abundance_hist(engine.read_input(input_path), k, canonical=not forward, nbins=max_count + 1,
-                              fmt=input_format)
+                              fmt=input_format, min_qual=min_qual, phred_offset=int(phred_offset))
     with open(output_path, "wb") as fh:
         fh.write(engine.format_hist(h))
     logging.info("That's all!")
