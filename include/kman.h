@@ -570,6 +570,29 @@ int kman_tag_batches(kman_ctx *ctx, uint64_t *d_keys, uint64_t n, uint32_t key_b
 int kman_or_u64(kman_ctx *ctx, uint64_t *d_v, uint64_t n, uint64_t value);
 int kman_widen_u32(kman_ctx *ctx, const uint32_t *d_in, uint64_t *d_out, uint64_t n, uint64_t value);
 int kman_memcpy_d2d(kman_ctx *ctx, void *dst, const void *src, size_t bytes);
+
+/* ------------------------------------------------------- abundance filter
+ * kman_filter_counts: stable compaction of count rows, keeping those with
+ *   lo <= count <= hi in their order; *n_out = the rows kept.
+ *   d_keys     W planes of n keys, plane j at d_keys + j * stride (W = 1: the
+ *              rows of kman_finish / kman_groups / kman_rle_count, any stride;
+ *              W > 1: the word planes of kman_rle_words, stride >= n)
+ *   d_counts   n counts of count_bytes (4 or 8)
+ *   outputs    both NULL: the rows are only counted (one read of the counts);
+ *              equal to the inputs: compacted in place; apart from the inputs
+ *              and from each other: written there, the inputs left as they
+ *              are (output planes at the same stride).  Anything else
+ *              (outputs that overlap the inputs in part, one output NULL) is
+ *              KMAN_EINVAL.
+ *   n == 0 or lo > hi: *n_out = 0, nothing launched, no error.
+ *   One pass over tiles of KMAN_FILTER_TILE rows for W = 1 (12 or 16 B read
+ *   per row, as many written per kept row); W > 1: one pass per plane and one
+ *   for the counts, each reading the counts.  Synchronises. */
+#define KMAN_FILTER_TILE 4096
+int kman_filter_counts(kman_ctx *ctx, const uint64_t *d_keys, uint32_t W, uint64_t stride, const void *d_counts,
+                       uint32_t count_bytes, uint64_t n, uint64_t lo, uint64_t hi, uint64_t *d_okeys,
+                       void *d_ocounts, uint64_t *n_out);
+
 /* kman_rebase_pos: uniq pos tagged with their source shard (bits 56-63) ->
  *   global pos: (pos & (2^56 - 1)) + (offsets[source] << 1), offsets = the
  *   global base index of each shard's first base (host array, nsrc <= 256).

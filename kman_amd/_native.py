@@ -40,6 +40,7 @@ KMAN_FINISH_SORT = 0
 KMAN_FINISH_COUNT = 1
 KMAN_FINISH_UNIQ = 2
 KMAN_PARSE_IN_RECORD = 1
+KMAN_FILTER_TILE = 4096  # rows per tile of kman_filter_counts (include/kman.h)
 
 
 def KMAN_HIST_LO(b: int) -> int:
@@ -197,6 +198,10 @@ SIGNATURES = {
     "kman_or_u64": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64]),
     "kman_widen_u32": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64]),
     "kman_memcpy_d2d": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
+    "kman_filter_counts": (
+        c_int, [c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_uint32, c_uint64, c_uint64, c_uint64, c_void_p,
+                c_void_p, POINTER(c_uint64)],
+    ),
     "kman_extract_wide": (
         c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64,
                 POINTER(c_uint64)],

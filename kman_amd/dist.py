@@ -506,6 +506,9 @@ class DistPipeline:
         self.canonical, self.rc = canonical, rc and not canonical
         self.path, self.max_round_items, self.reload, self.mem_frac = path, max_round_items, reload, mem_frac
         self.reparse, self.ordered = reparse, ordered
+        # count mode: text() prints the rows whose count is in this range
+        # (min, max | None); set by the caller, (1, None) prints them all
+        self.count_range = (1, None)
         # overlapped rounds (round_pieces): opt-in (overlap=True or
         # KMAN_DIST_OVERLAP=1) until a run on two or more GPUs has passed the
         # dist region tests with it; their all-to-alls run on a second
@@ -1234,7 +1237,16 @@ class DistPipeline:
         ok_, ov_, vb = self._out
         if self.mode == "count":
             r = engine.CountResult(ok_, ov_, vb, self.n_out, self.k)
-            return bytes(engine.emit_count(self.dev, r) or b"")
+            if self.count_range == (1, None):
+                return bytes(engine.emit_count(self.dev, r) or b"")
+            # out of place: later steps, the benchmark and kman_row_digest read
+            # the rows of _out again.  A rank left with no row still returns
+            # its (empty) text: emit_gen's collectives need every rank
+            f = engine.filtered_copy(self.dev, r, *self.count_range)
+            try:
+                return bytes(engine.emit_count(self.dev, f) or b"")
+            finally:
+                engine.free_result(f)
         pos = self.dev.alloc(8 * max(1, self.n_out))
         try:
             N.check(self.dev.ctx, N.lib().kman_memcpy_d2d(self.dev.ctx, c_void_p(pos.ptr), c_void_p(ov_.ptr),

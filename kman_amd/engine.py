@@ -1486,7 +1486,9 @@ class Words:
 
 @dataclass
 class WordsResult:
-    """count / uniq rows of k > 32: keys as W word planes (stride n)."""
+    """count / uniq rows of k > 32: keys as W word planes, row j's word q at
+    words[q * stride + j] (stride: max(n, 1) of the rows as they were made; a
+    filter_counts lowers n and leaves the planes where they are)."""
 
     words: DeviceBuffer
     vals: DeviceBuffer
@@ -1494,6 +1496,11 @@ class WordsResult:
     n: int
     k: int
     mode: str
+    stride: Optional[int] = None
+
+    def __post_init__(self):
+        if self.stride is None:
+            self.stride = max(self.n, 1)
 
     @property
     def W(self) -> int:
@@ -1610,7 +1617,7 @@ def rle_words(w: Words, mode: str) -> WordsResult:
         ov.free()
         raise
     # (planes keep the input's stride n: row j's word q at ow[q * n + j])
-    return WordsResult(ow, ov, vb, int(out.value), w.k, mode)
+    return WordsResult(ow, ov, vb, int(out.value), w.k, mode, stride=max(n, 1))
 
 
 def words_groups(p: Parsed, k: int, rc: bool, mode: str, canonical: bool = False) -> Optional[WordsResult]:
@@ -1649,26 +1656,102 @@ def decode_words(row, k: int) -> str:
     return "".join(decode_key(int(x), h if j == 0 else 32) for j, x in enumerate(row))
 
 
-def join_groups(p: Parsed, k: int, rc: bool, mode: str, max_keys: Optional[int] = None):
+def check_count_range(min_count=1, max_count=None) -> Tuple[int, Optional[int]]:
+    """The abundance range of filter_counts, checked: integers >= 1,
+    `max_count` None (no upper bound) or >= `min_count`."""
+    for name, v in (("min_count", min_count), ("max_count", max_count)):
+        if v is None and name == "max_count":
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise AssertionError("%s must be an integer >= 1, got %r" % (name, v))
+    if max_count is not None and min_count > max_count:
+        raise AssertionError("min_count %d is greater than max_count %d" % (min_count, max_count))
+    return int(min_count), None if max_count is None else int(max_count)
+
+
+def _count_rows(r):
+    """(key planes ptr, W, stride, counts ptr, count bytes) of a count result."""
+    if isinstance(r, WordsResult):
+        if r.mode != "count":
+            raise ValueError("filter_counts takes count rows, not uniq rows")
+        return r.words.ptr, r.W, r.stride, r.vals.ptr, r.val_bytes
+    if not isinstance(r, CountResult):
+        raise ValueError("filter_counts takes a CountResult or a count-mode WordsResult")
+    return r.ukeys.ptr, 1, max(r.n, 1), r.counts.ptr, r.count_bytes
+
+
+def _filter_call(dev: Device, r, lo: int, hi: int, okeys, ocounts) -> int:
+    kp, W, stride, cp, cb = _count_rows(r)
+    out = c_uint64(0)
+    N.check(dev.ctx, N.lib().kman_filter_counts(dev.ctx, c_void_p(kp), W, stride, c_void_p(cp), cb, r.n, lo, hi,
+                                                c_void_p(okeys), c_void_p(ocounts), byref(out)), "kman_filter_counts")
+    return int(out.value)
+
+
+_U64_MAX = (1 << 64) - 1
+
+
+def filter_counts(dev: Device, r, min_count: int = 1, max_count: Optional[int] = None):
+    """Keep the rows of a count result (CountResult, or a count-mode
+    WordsResult) whose count is in [min_count, max_count], in their order, in
+    place on the device (kman_filter_counts): r.n becomes the rows kept, the
+    buffers (and a WordsResult's stride) stay.  Returns r.  The identity
+    range (min_count <= 1, no max_count) launches nothing."""
+    if r is None or (min_count <= 1 and max_count is None):
+        return r
+    lo, hi = check_count_range(max(1, min_count), max_count)
+    kp, _, _, cp, _ = _count_rows(r)
+    r.n = _filter_call(dev, r, lo, _U64_MAX if hi is None else hi, kp, cp)
+    return r
+
+
+def filtered_copy(dev: Device, r: CountResult, min_count: int = 1, max_count: Optional[int] = None) -> CountResult:
+    """filter_counts out of place: the kept rows of a CountResult in fresh
+    buffers sized by a counting call first; r and its buffers are left as
+    they are (rows that are read again, such as a pipeline's)."""
+    lo, hi = check_count_range(min_count, max_count)
+    hi = _U64_MAX if hi is None else hi
+    n = _filter_call(dev, r, lo, hi, None, None)
+    ok_ = dev.alloc(8 * max(n, 1))
+    oc_ = dev.alloc(r.count_bytes * max(n, 1))
+    try:
+        if n:
+            got = _filter_call(dev, r, lo, hi, ok_.ptr, oc_.ptr)
+            assert got == n
+    except BaseException:
+        ok_.free()
+        oc_.free()
+        raise
+    return CountResult(ok_, oc_, r.count_bytes, n, r.k)
+
+
+def join_groups(p: Parsed, k: int, rc: bool, mode: str, max_keys: Optional[int] = None, canonical: bool = False):
     """The count / uniq result of the whole stream of p on the device, by the
     fastest path that takes it: the region path (kman_groups); the multi-batch
     join (RangedJoin) when the single-batch general path does not fit the
     free HBM or max_keys asks for it; else the general path (extract_sorted +
     rle_*); k > 32: the word-pair path (wide_groups).  None when the stream
-    has no k-mers."""
+    has no k-mers.  canonical: the rows of min(k-mer, reverse complement)
+    (count only; `rc` is then moot, both strands fold into one key); a
+    sub-path that cannot take canonical keys raises NotImplementedError."""
+    if canonical and mode == "uniq":
+        raise ValueError("canonical k-mers are counted (config 5), not uniq'd")
     if k > MAX_K:
-        return words_groups(p, k, rc, mode)
-    r = groups(p, k, rc, mode) if max_keys is None else None
+        return words_groups(p, k, rc, mode, canonical)
+    r = groups(p, k, rc, mode, canonical) if max_keys is None else None
     if r is None and max_keys is None and p.n_bases:
         # outside kman_groups (too many k-mers for its regions, -r on large
         # inputs, skewed keys): the key rounds of the multi-GPU path on one GPU
         from . import dist
 
-        r = dist.local_groups(p, k, rc, mode)
-    if r is None and (max_keys is not None or not _fits(p, k, rc, mode)):
+        r = dist.local_groups(p, k, rc, mode, canonical)
+    if r is None and (max_keys is not None or not _fits(p, k, rc and not canonical, mode)):
+        if canonical:
+            # (RangedJoin cuts the stream by forward-key ranges: kman_extract_range has no canonical keys)
+            raise NotImplementedError("canonical k-mers through the multi-batch join (RangedJoin)")
         r = ranged_groups(p, k, rc, mode, max_keys)
     if r is None:
-        km = extract_sorted(p, k, rc, want_pos=mode == "uniq")
+        km = extract_sorted(p, k, rc, want_pos=mode == "uniq", canonical=canonical)
         try:
             if km.n == 0:
                 return None
@@ -1695,11 +1778,11 @@ def _emit_words(p: Parsed, r: WordsResult, sink=None):
     with KMAN_HOST_FORMAT=1."""
     dev, L = p.dev, N.lib()
     vb = r.val_bytes
-    # (row j's word q at words[q * n + j]: a slice of rows is the same planes offset by i0)
+    # (row j's word q at words[q * stride + j]: a slice of rows is the same planes offset by i0)
     if not host_format():
         if r.mode == "count":
             def call(i0, m, d_out, cap, used):
-                return L.kman_format_count_words_dev(dev.ctx, c_void_p(r.words.ptr + 8 * i0), max(r.n, 1),
+                return L.kman_format_count_words_dev(dev.ctx, c_void_p(r.words.ptr + 8 * i0), r.stride,
                                                      c_void_p(r.vals.ptr + vb * i0), vb, m, r.k, d_out, cap,
                                                      byref(used))
 
@@ -1709,7 +1792,7 @@ def _emit_words(p: Parsed, r: WordsResult, sink=None):
             D = len(str(p.n_bases + r.k))
 
             def call(i0, m, d_out, cap, used):
-                return L.kman_format_uniq_words_dev(dev.ctx, c_void_p(r.words.ptr + 8 * i0), max(r.n, 1),
+                return L.kman_format_uniq_words_dev(dev.ctx, c_void_p(r.words.ptr + 8 * i0), r.stride,
                                                     c_void_p(r.vals.ptr + vb * i0), vb, m, r.k,
                                                     c_void_p(nm.names.ptr), c_void_p(nm.off.ptr), c_void_p(nm.rec.ptr),
                                                     nm.n_records, d_out, cap, byref(used))
@@ -1717,15 +1800,15 @@ def _emit_words(p: Parsed, r: WordsResult, sink=None):
             return _format_dev(dev, r.n, 1 + nm.max_name + 1 + D + 1 + D + 3 + r.k + 1, call, sink)
         finally:
             nm.free()
-    words = dev.download(r.words, r.W * max(r.n, 1), np.uint64)
+    words = dev.download(r.words, r.W * r.stride, np.uint64)
     vals = dev.download(r.vals, r.n, np.uint32 if vb == 4 else np.uint64)
     if r.mode == "count":
-        return _to(sink, _format(L.kman_format_count_words, words.ctypes.data_as(c_void_p), max(r.n, 1),
+        return _to(sink, _format(L.kman_format_count_words, words.ctypes.data_as(c_void_p), r.stride,
                                  vals.ctypes.data_as(c_void_p), vb, r.n, r.k))
     names = ctypes.create_string_buffer(p.names_blob, max(1, len(p.names_blob)))
     off = np.ascontiguousarray(p.name_off, dtype=np.uint64)
     rs = np.ascontiguousarray(p.rec_seq, dtype=np.uint64)
-    return _to(sink, _format(L.kman_format_uniq_words, words.ctypes.data_as(c_void_p), max(r.n, 1),
+    return _to(sink, _format(L.kman_format_uniq_words, words.ctypes.data_as(c_void_p), r.stride,
                              vals.ctypes.data_as(c_void_p), vb, r.n, r.k, names, off.ctypes.data_as(c_void_p),
                              rs.ctypes.data_as(c_void_p), p.n_records))
 

@@ -156,6 +156,44 @@ class KJoiner:
             if not isinstance(memory, self.MEMORY):
                 raise AssertionError
             self.__memory = memory
+        self.__min_count, self.__max_count, self.__canonical = 1, None, False
+
+    @property
+    def min_count(self) -> int:
+        """SEQ_COUNT: rows with a smaller count are dropped (default 1: none)."""
+        return self.__min_count
+
+    @min_count.setter
+    def min_count(self, min_count) -> None:
+        if type(min_count) is not int or min_count < 1:
+            raise AssertionError
+        self.__min_count = min_count
+
+    @property
+    def max_count(self):
+        """SEQ_COUNT: rows with a larger count are dropped (default None: none)."""
+        return self.__max_count
+
+    @max_count.setter
+    def max_count(self, max_count) -> None:
+        if max_count is not None and (type(max_count) is not int or max_count < 1):
+            raise AssertionError
+        self.__max_count = max_count
+
+    @property
+    def canonical(self) -> bool:
+        """SEQ_COUNT: count min(k-mer, reverse complement) (default False)."""
+        return self.__canonical
+
+    @canonical.setter
+    def canonical(self, canonical) -> None:
+        if type(canonical) is not bool:
+            raise AssertionError
+        self.__canonical = canonical
+
+    @property
+    def filtered(self) -> bool:
+        return self.__min_count > 1 or self.__max_count is not None
 
     @property
     def mode(self):
@@ -198,6 +236,12 @@ class KJoiner:
         print("Joining...")
         from .launch import ShardedSource
 
+        if (self.filtered or self.canonical) and self.mode != self.MODE.SEQ_COUNT:
+            raise AssertionError("min_count / max_count / canonical are options of SEQ_COUNT, not of %s"
+                                 % self.mode.name)
+        engine.check_count_range(self.min_count, self.max_count)
+        if self.canonical:
+            canonical_stream(batches)
         sharded = [b for b in batches if b is not None and isinstance(b.source, ShardedSource)]
         if sharded:
             # one rank of a multi-GPU run (kman_amd/launch.py): the key rounds
@@ -206,18 +250,48 @@ class KJoiner:
             if self.mode.name.startswith("VEC_") or others or len(sharded) != 1:
                 raise NotImplementedError("a multi-GPU launch joins the FastaBatcher shard batches by UNIQUE / "
                                           "SEQ_COUNT only")
-            sharded[0].source.join(self.mode == self.MODE.SEQ_COUNT, outpath)
+            sharded[0].source.join(self.mode == self.MODE.SEQ_COUNT, outpath, self.min_count, self.max_count)
             return
         if self.mode.name.startswith("VEC_"):
             join_vectors(batches, self.mode == self.MODE.VEC_COUNT_MASKED, outpath)
             return
         with open(outpath, "wb") as OH:
-            join_bytes(batches, self.mode == self.MODE.SEQ_COUNT, sink=OH)
+            join_bytes(batches, self.mode == self.MODE.SEQ_COUNT, sink=OH, min_count=self.min_count,
+                       max_count=self.max_count, canonical=self.canonical)
 
 
-def join_bytes(batches: List[Batch], count: bool, sink=None):
+def canonical_stream(batches: List[Batch]):
+    """The source that canonical counting can take -- the batches are the
+    whole stream of one FASTA / FASTQ source extracted without -r (the
+    canonical keys come from the codes, not from the batches' forward keys;
+    with -r the strands are already in the stream) -- else AssertionError.
+    None when there is nothing to join.  No device work."""
+    from .launch import ShardedSource
+
+    if any(b is not None and isinstance(b.source, ShardedSource) for b in batches):
+        raise AssertionError("canonical counting runs on one GPU (rank 0 alone under a launch)")
+    entries = _entries(batches)
+    if not entries:
+        return None
+    whole = _whole_stream(entries)
+    if whole is None or whole.rc:
+        raise AssertionError("canonical counting needs the whole k-mer stream of one input extracted without "
+                             "reverse complements (no -r, no -B, one source)")
+    return whole
+
+
+def join_bytes(batches: List[Batch], count: bool, sink=None, min_count: int = 1, max_count=None,
+               canonical: bool = False):
     """Device join of the batches: gather + stable sort + RLE, then format.
-    Returns the output text, or writes it to the binary file `sink`."""
+    Returns the output text, or writes it to the binary file `sink`.
+    count: every count result is filtered to [min_count, max_count] on the
+    device just before it is formatted (engine.filter_counts); canonical:
+    the rows of min(k-mer, reverse complement) (canonical_stream)."""
+    if (min_count > 1 or max_count is not None or canonical) and not count:
+        raise AssertionError("min_count / max_count / canonical are options of the count join")
+    engine.check_count_range(min_count, max_count)
+    if canonical:
+        canonical_stream(batches)
     entries = _entries(batches)
     if not entries:
         logging.error("nothing to crawl")  # join.py:110; the output stays empty
@@ -231,11 +305,13 @@ def join_bytes(batches: List[Batch], count: bool, sink=None):
         # straight from the codes: region path, else the multi-batch join when
         # one batch does not fit the HBM, else the general path (no copy of a
         # cached extraction either way)
-        r = engine.join_groups(whole.parsed, whole.k, whole.rc, "count" if count else "uniq")
+        r = engine.join_groups(whole.parsed, whole.k, whole.rc, "count" if count else "uniq", canonical=canonical)
         phases.mark("step")
         if r is None:
             return None if sink is not None else b""
         try:
+            if count:
+                engine.filter_counts(whole.dev, r, min_count, max_count)
             if isinstance(r, engine.WordsResult):
                 return engine._emit_words(whole.parsed, r, sink)
             if count:
@@ -254,8 +330,8 @@ def join_bytes(batches: List[Batch], count: bool, sink=None):
             km.free()
         try:
             if count:
-                return engine._emit_words(_any_parsed(srcs), r, sink)
-            rows = engine.download_words(dev, r.words, r.n, k, max(r.n, 1))
+                return engine._emit_words(_any_parsed(srcs), engine.filter_counts(dev, r, min_count, max_count), sink)
+            rows = engine.download_words(dev, r.words, r.n, k, r.stride)
             pos = dev.download(r.vals, r.n, np.uint64)
         finally:
             r.free()
@@ -264,7 +340,7 @@ def join_bytes(batches: List[Batch], count: bool, sink=None):
         if count:
             r = engine.rle_count(km, dev)
             try:
-                return engine.emit_count(dev, r, sink)
+                return engine.emit_count(dev, engine.filter_counts(dev, r, min_count, max_count), sink)
             finally:
                 r.ukeys.free()
                 r.counts.free()

@@ -327,10 +327,14 @@ class ShardedSource:
             remove_id(tag)  # (every rank has joined the communicator)
         return pipe
 
-    def join(self, count: bool, outpath: str) -> int:
+    def join(self, count: bool, outpath: str, min_count: int = 1, max_count=None) -> int:
         """Count / uniq of the whole FASTA across the ranks into `outpath`
-        (every rank writes its slice); returns the file's size."""
+        (every rank writes its slice); returns the file's size.  count: every
+        rank keeps its rows with a count in [min_count, max_count]."""
+        if not count and (min_count > 1 or max_count is not None):
+            raise AssertionError("min_count / max_count are options of the count join")
         pipe = self._pipe("count" if count else "uniq")
+        pipe.count_range = engine.check_count_range(min_count, max_count)
         try:
             pipe.step()
             return pipe.comm.run(pipe.emit_gen(outpath))

@@ -97,5 +97,20 @@ def phred_offset():
                         help="ASCII offset of the fastq quality bytes, for --min-qual. Default: 33")
 
 
+def min_count():
+    return click.option("--min-count", "-L", "min_count", type=click.IntRange(min=1), default=1,
+                        help="SEQ_COUNT: leave out k-mers seen fewer times than this. Default: 1 (all)")
+
+
+def max_count():
+    return click.option("--max-count", "-U", "max_count", type=click.IntRange(min=1), default=None,
+                        help="SEQ_COUNT: leave out k-mers seen more times than this. Default: no limit")
+
+
+def canonical():
+    return click.option("--canonical", "canonical", is_flag=True,
+                        help="SEQ_COUNT: count canonical k-mers, min(k-mer, reverse complement); not with -r or -B")
+
+
 def re_sort():
     return click.option("--re-sort", "-R", is_flag=True, help="Force batch re-sorting, when loaded with -B.")

@@ -74,15 +74,20 @@ INPUT runs on rank 0 alone).
 @args.input_format()
 @args.min_qual()
 @args.phred_offset()
+@args.min_count()
+@args.max_count()
+@args.canonical()
 def count(input_path: str, output_path: str, k: int, reverse: bool = False, scan_mode: str = "KMERS",
           batch_size: int = 1000000, batch_mode: str = "APPEND", previous_batches: Optional[str] = None,
           count_mode: str = "SEQ_COUNT", memory_mode: str = "NORMAL", threads: int = 1,
           tmp: str = tempfile.gettempdir(), re_sort: bool = False, input_format: str = "auto",
-          min_qual: int = 0, phred_offset: str = "33") -> None:
+          min_qual: int = 0, phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None,
+          canonical: bool = False) -> None:
     input_file_exists(input_path)
     _check_min_qual(min_qual, input_path, input_format, previous_batches)
+    _check_count_options(min_count, max_count, canonical, count_mode, reverse, previous_batches)
     set_tempdir(tmp)
-    dist = _multi_gpu(k, previous_batches, count_mode, input_path, input_format)
+    dist = _multi_gpu(k, previous_batches, count_mode, input_path, input_format, canonical=canonical)
     if dist is None:
         return  # (a rank other than 0, for work outside the multi-GPU domain)
     if previous_batches is not None:
@@ -90,9 +95,26 @@ def count(input_path: str, output_path: str, k: int, reverse: bool = False, scan
     else:
         batches = _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist,
                            input_format, min_qual, int(phred_offset))
-    prep_joiner(KJoinerThreading(KJoiner.MODE[count_mode], KJoiner.MEMORY[memory_mode]), len(batches),
-                threads).join(batches, output_path)
+    joiner = prep_joiner(KJoinerThreading(KJoiner.MODE[count_mode], KJoiner.MEMORY[memory_mode]), len(batches),
+                         threads)
+    joiner.min_count, joiner.max_count, joiner.canonical = min_count, max_count, canonical
+    joiner.join(batches, output_path)
     logging.info("That's all!")
+
+
+def _check_count_options(min_count: int, max_count: Optional[int], canonical: bool, count_mode: str, reverse: bool,
+                         previous_batches: Optional[str]) -> None:
+    """The abundance range and --canonical of `kmer count`: what they cannot
+    be combined with is refused before any device work or output."""
+    filtered = min_count > 1 or max_count is not None
+    if max_count is not None and min_count > max_count:
+        raise AssertionError("--min-count %d is greater than --max-count %d" % (min_count, max_count))
+    if (filtered or canonical) and count_mode != "SEQ_COUNT":
+        raise AssertionError("--min-count / --max-count / --canonical need -m SEQ_COUNT, not %s" % count_mode)
+    if canonical and reverse:
+        raise AssertionError("--canonical with -r: the strands are already folded into one k-mer")
+    if canonical and previous_batches is not None:
+        raise AssertionError("--canonical with -B: canonical k-mers come from the INPUT, not from reloaded batches")
 
 
 def _check_min_qual(min_qual: int, input_path: str, input_format: str,
@@ -111,13 +133,18 @@ def _is_fastq(input_path: Optional[str], input_format: str) -> bool:
 
 
 def _multi_gpu(k: int, previous_batches: Optional[str], count_mode: str = "SEQ_COUNT",
-               input_path: Optional[str] = None, input_format: str = "auto") -> Optional[bool]:
+               input_path: Optional[str] = None, input_format: str = "auto", *,
+               canonical: bool = False) -> Optional[bool]:
     """Under a one-process-per-GPU launch (kman_amd/launch.py): True = this
     rank joins across the GPUs; False = the single-GPU path (no launch, or
     rank 0 alone for work outside the multi-GPU domain: k > 32, -B reloads,
-    VEC_* modes, fastq input); None = a rank that leaves that work to rank 0."""
+    VEC_* modes, fastq input, count --canonical); None = a rank that leaves
+    that work to rank 0."""
     if not launch.distributed():
         return False
+    if canonical and k > 1:
+        launch.log_solo("count --canonical")  # (ordered canonical rows across ranks: DESIGN §8)
+        return False if launch.solo_rank() else None
     if k > 1 and previous_batches is None and _is_fastq(input_path, input_format):
         launch.log_solo("fastq input")  # (the byte-range shards cut FASTA only)
         return False if launch.solo_rank() else None
