@@ -593,6 +593,47 @@ int kman_filter_counts(kman_ctx *ctx, const uint64_t *d_keys, uint32_t W, uint64
                        uint32_t count_bytes, uint64_t n, uint64_t lo, uint64_t hi, uint64_t *d_okeys,
                        void *d_ocounts, uint64_t *n_out);
 
+/* ------------------------------------------------------- two count tables
+ * kman_match_counts: look every row of table A up in table B.  A and B are
+ *   rows (u64 key, count) each STRICTLY ASCENDING in key (distinct, sorted:
+ *   the rows of kman_groups / kman_finish / kman_rle_count); this is not
+ *   checked -- rows that break it give wrong counts, never a wild address or
+ *   an endless loop.  For every row i of A, with ca = its count and cb = the
+ *   count of the row of B with the same key ("matched"; none: cb = 0):
+ *     KMAN_MATCH_RIGHT    out[i] = cb                      (the plain lookup)
+ *     KMAN_MATCH_LEFT     out[i] = matched ? ca : 0
+ *     KMAN_MATCH_MIN      out[i] = matched ? min(ca, cb) : 0
+ *     KMAN_MATCH_MAX      out[i] = matched ? max(ca, cb) : 0
+ *     KMAN_MATCH_SUM      out[i] = matched ? ca + cb : 0
+ *     KMAN_MATCH_ABSENT   out[i] = matched ? 0 : ca
+ *     KMAN_MATCH_ANY_SUM  out[i] = ca + cb                 (never 0 for ca >= 1)
+ *     KMAN_MATCH_ANY_MAX  out[i] = max(ca, cb)
+ *   Counts and out are 4 or 8 bytes wide, each chosen on its own; sums are
+ *   made in 64 bits, and a value that does not fit out_bytes is stored as the
+ *   largest value of that width.  Any other op or width: KMAN_EINVAL.
+ *   na == 0: nothing is launched; nb == 0: every row is unmatched and B is
+ *   not read.  RIGHT does not read A's counts, LEFT and ABSENT do not read
+ *   B's (they may be NULL).  The inputs are never written; d_out (na values)
+ *   must not overlap them (not checked).
+ *   A merge-path join: a split step cuts the merged order of A and B into
+ *   tiles of KMAN_MATCH_TILE rows (the splits in the context's scratch), a
+ *   tile kernel matches each tile's A rows against its B rows in LDS, so the
+ *   work per block does not depend on na : nb.  8 + a_count_bytes read per A
+ *   row, 8 + b_count_bytes per B row, out_bytes written per A row.
+ *   Synchronises. */
+#define KMAN_MATCH_TILE 2048
+#define KMAN_MATCH_RIGHT 0
+#define KMAN_MATCH_LEFT 1
+#define KMAN_MATCH_MIN 2
+#define KMAN_MATCH_MAX 3
+#define KMAN_MATCH_SUM 4
+#define KMAN_MATCH_ABSENT 5
+#define KMAN_MATCH_ANY_SUM 6
+#define KMAN_MATCH_ANY_MAX 7
+int kman_match_counts(kman_ctx *ctx, const uint64_t *d_akeys, const void *d_acounts, uint32_t a_count_bytes,
+                      uint64_t na, const uint64_t *d_bkeys, const void *d_bcounts, uint32_t b_count_bytes,
+                      uint64_t nb, int op, void *d_out, uint32_t out_bytes);
+
 /* kman_rebase_pos: uniq pos tagged with their source shard (bits 56-63) ->
  *   global pos: (pos & (2^56 - 1)) + (offsets[source] << 1), offsets = the
  *   global base index of each shard's first base (host array, nsrc <= 256).

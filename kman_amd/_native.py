@@ -41,6 +41,15 @@ KMAN_FINISH_COUNT = 1
 KMAN_FINISH_UNIQ = 2
 KMAN_PARSE_IN_RECORD = 1
 KMAN_FILTER_TILE = 4096  # rows per tile of kman_filter_counts (include/kman.h)
+KMAN_MATCH_TILE = 2048  # merged rows (A + B) per tile of kman_match_counts (include/kman.h)
+KMAN_MATCH_RIGHT = 0
+KMAN_MATCH_LEFT = 1
+KMAN_MATCH_MIN = 2
+KMAN_MATCH_MAX = 3
+KMAN_MATCH_SUM = 4
+KMAN_MATCH_ABSENT = 5
+KMAN_MATCH_ANY_SUM = 6
+KMAN_MATCH_ANY_MAX = 7
 
 
 def KMAN_HIST_LO(b: int) -> int:
@@ -201,6 +210,10 @@ SIGNATURES = {
     "kman_filter_counts": (
         c_int, [c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_uint32, c_uint64, c_uint64, c_uint64, c_void_p,
                 c_void_p, POINTER(c_uint64)],
+    ),
+    "kman_match_counts": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_void_p, c_uint32, c_uint64, c_int,
+                c_void_p, c_uint32],
     ),
     "kman_extract_wide": (
         c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64,

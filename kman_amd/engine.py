@@ -1725,6 +1725,118 @@ def filtered_copy(dev: Device, r: CountResult, min_count: int = 1, max_count: Op
     return CountResult(ok_, oc_, r.count_bytes, n, r.k)
 
 
+# ------------------------------------------------- two count tables (set ops)
+
+MATCH_OPS = {
+    "right": N.KMAN_MATCH_RIGHT, "left": N.KMAN_MATCH_LEFT, "min": N.KMAN_MATCH_MIN, "max": N.KMAN_MATCH_MAX,
+    "sum": N.KMAN_MATCH_SUM, "absent": N.KMAN_MATCH_ABSENT, "any_sum": N.KMAN_MATCH_ANY_SUM,
+    "any_max": N.KMAN_MATCH_ANY_MAX,
+}
+SET_OPS = {  # op -> the `counts` choices it takes, the default first
+    "intersect": ("left", "right", "min", "max", "sum"),
+    "subtract": ("left",),
+    "union": ("sum", "max"),
+}
+
+
+def check_set_op(op: str, counts: Optional[str] = None) -> str:
+    """The `counts` choice of set_op(op), checked (AssertionError); None: the
+    op's default."""
+    if op not in SET_OPS:
+        raise AssertionError("op must be one of %s, got %r" % (", ".join(SET_OPS), op))
+    if counts is None:
+        return SET_OPS[op][0]
+    if counts not in SET_OPS[op]:
+        raise AssertionError("--counts %s: --op %s takes %s" % (counts, op, " | ".join(SET_OPS[op])))
+    return counts
+
+
+def empty_count(dev: Device, k: int) -> CountResult:
+    """The count table of an input without k-mers: the empty set."""
+    return CountResult(dev.alloc(8), dev.alloc(4), 4, 0, k)
+
+
+def _match_bytes(a: CountResult, b: CountResult) -> int:
+    return 8 if 8 in (a.count_bytes, b.count_bytes) else 4
+
+
+def match_counts(dev: Device, a: CountResult, b: CountResult, op: str = "right") -> DeviceBuffer:
+    """kman_match_counts: one value per row of `a` from the row of `b` with
+    the same key (MATCH_OPS; include/kman.h), as a fresh device vector of
+    a.n values, 4 bytes wide unless either table's counts are 8.  `a` and `b`
+    are key-sorted distinct count rows of one k (join_groups(.., "count"))."""
+    if op not in MATCH_OPS:
+        raise AssertionError("match op must be one of %s, got %r" % (", ".join(MATCH_OPS), op))
+    if a.k != b.k:
+        raise AssertionError("the two tables hold k-mers of different k: %d and %d" % (a.k, b.k))
+    ob = _match_bytes(a, b)
+    out = dev.alloc(ob * max(a.n, 1))
+    try:
+        N.check(dev.ctx, N.lib().kman_match_counts(
+            dev.ctx, c_void_p(a.ukeys.ptr), c_void_p(a.counts.ptr), a.count_bytes, a.n, c_void_p(b.ukeys.ptr),
+            c_void_p(b.counts.ptr), b.count_bytes, b.n, MATCH_OPS[op], c_void_p(out.ptr), ob), "kman_match_counts")
+    except BaseException:
+        out.free()
+        raise
+    return out
+
+
+def _matched_rows(dev: Device, a: CountResult, b: CountResult, op: str, lo: int = 1,
+                  hi: Optional[int] = None) -> CountResult:
+    """The rows (key of a, match_counts(a, b, op)) whose value is in [lo, hi],
+    in fresh buffers: the match vector, then one out-of-place filter over a's
+    keys and that vector (rows whose value is 0 are dropped: lo >= 1)."""
+    v = match_counts(dev, a, b, op)
+    try:
+        return filtered_copy(dev, CountResult(a.ukeys, v, _match_bytes(a, b), a.n, a.k), lo, hi)
+    finally:
+        v.free()
+
+
+def set_op(dev: Device, a: CountResult, b: CountResult, op: str, counts: Optional[str] = None, min_count: int = 1,
+           max_count: Optional[int] = None) -> CountResult:
+    """Set operations on two count tables of one k, on the device; a fresh
+    CountResult (key-sorted, distinct), `a` and `b` left as they are.
+      intersect  the rows of a whose key is in b; counts: left (default, a's) |
+                 right (b's) | min | max | sum
+      subtract   the rows of a whose key is not in b, with a's counts
+      union      every key of either; counts: sum (default) | max
+    Only rows whose resulting count is in [max(1, min_count), max_count] are
+    kept.  intersect / subtract: kman_match_counts + one out-of-place
+    kman_filter_counts (the range costs no pass of its own); union: a's rows
+    with ANY_SUM / ANY_MAX, b's rows absent from a, one 2-run kman_merge_runs,
+    then the range.  No row is downloaded."""
+    counts = check_set_op(op, counts)
+    if a.k != b.k:
+        raise AssertionError("the two tables hold k-mers of different k: %d and %d" % (a.k, b.k))
+    lo, hi = check_count_range(max(1, min_count) if isinstance(min_count, (int, np.integer)) else min_count,
+                               max_count)
+    if op == "intersect":
+        return _matched_rows(dev, a, b, counts, lo, hi)
+    if op == "subtract":
+        return _matched_rows(dev, a, b, "absent", lo, hi)
+    vb = _match_bytes(a, b)
+    va = only_b = ok_ = oc_ = None
+    try:
+        va = match_counts(dev, a, b, "any_" + counts)
+        only_b = _matched_rows(dev, b, a, "absent")
+        n = a.n + only_b.n
+        ok_ = dev.alloc(8 * max(n, 1))
+        oc_ = dev.alloc(vb * max(n, 1))
+        runs = (N.Run * 2)(N.Run(a.ukeys.ptr, va.ptr, a.n), N.Run(only_b.ukeys.ptr, only_b.counts.ptr, only_b.n))
+        N.check(dev.ctx, N.lib().kman_merge_runs(dev.ctx, runs, 2, vb, c_void_p(ok_.ptr), c_void_p(oc_.ptr), None,
+                                                 None), "kman_merge_runs")
+        r = CountResult(ok_, oc_, vb, n, a.k)
+        filter_counts(dev, r, lo, hi)
+        ok_ = oc_ = None  # (the result's now)
+        return r
+    finally:
+        for buf in (va, ok_, oc_):
+            if buf is not None:
+                buf.free()
+        free_result(only_b)
+
+
 def join_groups(p: Parsed, k: int, rc: bool, mode: str, max_keys: Optional[int] = None, canonical: bool = False):
     """The count / uniq result of the whole stream of p on the device, by the
     fastest path that takes it: the region path (kman_groups); the multi-batch

@@ -112,5 +112,26 @@ def canonical():
                         help="SEQ_COUNT: count canonical k-mers, min(k-mer, reverse complement); not with -r or -B")
 
 
+def input_a():
+    return click.argument("input_a", metavar="INPUT_A", type=click.Path(exists=True, file_okay=True, readable=True))
+
+
+def input_b():
+    return click.argument("input_b", metavar="INPUT_B", type=click.Path(exists=True, file_okay=True, readable=True))
+
+
+def set_op():
+    return click.option("--op", "op", type=click.Choice(["intersect", "subtract", "union"], case_sensitive=True),
+                        required=True, help="intersect: k-mers of INPUT_A that occur in INPUT_B; subtract: those "
+                                            "that do not; union: the k-mers of either")
+
+
+def set_counts():
+    return click.option("--counts", "counts", type=click.Choice(["left", "right", "min", "max", "sum"],
+                                                                 case_sensitive=True),
+                        default=None, help="The count written for a k-mer.  intersect: left (INPUT_A's, default) | "
+                                           "right | min | max | sum; subtract: left; union: sum (default) | max")
+
+
 def re_sort():
     return click.option("--re-sort", "-R", is_flag=True, help="Force batch re-sorting, when loaded with -B.")

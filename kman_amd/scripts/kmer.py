@@ -2,6 +2,7 @@
 
 Same arguments, flags, defaults, outputs and errors as the reference CLI; the
 work runs on the GPU through kman_amd (FastaBatcher.do + KJoiner.join).
+``hist`` and ``sets`` are this engine's own commands.
 """
 
 from __future__ import annotations
@@ -294,6 +295,82 @@ def hist(input_path: str, output_path: str, k: int, forward: bool = False, max_c
     with open(output_path, "wb") as fh:
         fh.write(engine.format_hist(h))
     logging.info("That's all!")
+
+
+@main.command(name="sets", context_settings=CONTEXT_SETTINGS, help="""
+Set operations on the k-mers of two inputs: the k-mers of INPUT_A that also
+occur in INPUT_B (--op intersect), those that do not (--op subtract), or the
+k-mers of either (--op union), written to OUTPUT as `count` writes them, one
+"SEQ<TAB>N" line per k-mer in ascending order.
+
+Not part of the reference kman CLI.  Both inputs are counted on the GPU and
+their tables are matched there (kman_match_counts); no table goes through a
+text file.  INPUT_A, INPUT_B: fasta or fastq files, plain or gzipped, each
+detected on its own.  K <= 32.  -L / -U select by the count that is written.
+Launched one process per GPU, the command runs on rank 0 alone.
+""")
+@args.input_a()
+@args.input_b()
+@args.output_path(file_okay=True)
+@args.k()
+@args.set_op()
+@args.set_counts()
+@args.reverse()
+@args.canonical()
+@args.input_format()
+@args.min_qual()
+@args.phred_offset()
+@args.min_count()
+@args.max_count()
+def sets(input_a: str, input_b: str, output_path: str, k: int, op: str, counts: Optional[str] = None,
+         reverse: bool = False, canonical: bool = False, input_format: str = "auto", min_qual: int = 0,
+         phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None) -> None:
+    input_file_exists(input_a)
+    input_file_exists(input_b)
+    fastq = [_is_fastq(p, input_format) for p in (input_a, input_b)]
+    _check_sets_options(k, op, counts, reverse, canonical, min_qual, fastq, min_count, max_count)
+    if launch.distributed() and not launch.solo_rank():
+        launch.log_solo("kmer sets")  # (two whole tables on one GPU: DESIGN §8)
+        return
+    dev = engine.default_device()
+    tables = []
+    try:
+        for path, fq in zip((input_a, input_b), fastq):
+            # (A's parse buffers are freed before B is read)
+            p = engine.parse_file(dev, path, input_format, min_qual if fq else 0, int(phred_offset))
+            try:
+                engine.check_empty_names(p, k)
+                r = engine.join_groups(p, k, reverse, "count", canonical=canonical)
+            finally:
+                p.free()
+            tables.append(r if r is not None else engine.empty_count(dev, k))  # (no k-mers: the empty set)
+        r = engine.set_op(dev, tables[0], tables[1], op, counts, min_count, max_count)
+        try:
+            with open(output_path, "wb") as fh:
+                engine.emit_count(dev, r, fh)
+        finally:
+            engine.free_result(r)
+    finally:
+        for t in tables:
+            engine.free_result(t)
+    logging.info("That's all!")
+
+
+def _check_sets_options(k: int, op: str, counts: Optional[str], reverse: bool, canonical: bool, min_qual: int,
+                        fastq, min_count: int, max_count: Optional[int]) -> None:
+    """What `kmer sets` refuses, before any device work or output."""
+    if k <= 1:
+        raise AssertionError("k must be >= 1, got %d instead." % k)
+    if k > engine.MAX_K:
+        raise AssertionError("kmer sets takes K <= %d (one 64-bit key per k-mer), got %d: word keys are a stated "
+                             "limit of this command" % (engine.MAX_K, k))
+    if canonical and reverse:
+        raise AssertionError("--canonical with -r: the strands are already folded into one k-mer")
+    if min_qual > 0 and not any(fastq):
+        raise AssertionError("--min-qual needs fastq input: neither INPUT_A nor INPUT_B is fastq")
+    engine.check_set_op(op, counts)
+    if max_count is not None and min_count > max_count:
+        raise AssertionError("--min-count %d is greater than --max-count %d" % (min_count, max_count))
 
 
 if __name__ == "__main__":
