@@ -634,6 +634,57 @@ int kman_match_counts(kman_ctx *ctx, const uint64_t *d_akeys, const void *d_acou
                       uint64_t na, const uint64_t *d_bkeys, const void *d_bcounts, uint32_t b_count_bytes,
                       uint64_t nb, int op, void *d_out, uint32_t out_bytes);
 
+/* ------------------------------------------------- reads against a table
+ * Not in the reference: for every record of a parsed input, how many of its
+ * k-mer windows are rows of a count table, and the sum of those rows' counts.
+ *
+ * kman_table_index: a prefix index over nt STRICTLY ASCENDING 2k-bit keys
+ *   (the rows of kman_groups / kman_finish / kman_rle_count; not checked).
+ *   Writes 2^index_bits + 1 words: d_index[p] = the number of rows whose top
+ *   index_bits bits (of the 2k-bit key) are < p; d_index[2^index_bits] = nt.
+ *   1 <= index_bits <= min(2k, KMAN_SCREEN_MAX_INDEX_BITS), else KMAN_EINVAL.
+ *   nt == 0 is legal: an all-zero index, the keys are not read.  One thread
+ *   per entry, a lower bound over the keys in bits(nt) <= 64 steps.
+ *   Synchronises.
+ *
+ * kman_screen_records: d_codes, n_bases, k (2..32) and flags as for
+ *   kman_extract (codes 16-byte aligned and followed by 64 bytes of padding,
+ *   as the parsers write them); flags is 0 or KMAN_CANONICAL, anything else
+ *   KMAN_EINVAL.  d_rec_seq: n_records ascending first-base indices (equal
+ *   neighbours are empty records).  The table: nt rows (d_tkeys strictly
+ *   ascending, d_tcounts of t_count_bytes = 4 or 8) and the index that
+ *   kman_table_index made of it with the same k and index_bits.
+ *   d_out, three planes of n_records u64, zeroed by the call itself:
+ *     d_out[r]                  the valid windows that start in record r (k
+ *                               ACGT codes, no record start after the first)
+ *     d_out[n_records + r]      how many of them have their key (the canonical
+ *                               key under KMAN_CANONICAL) among the table's rows
+ *     d_out[2 * n_records + r]  the sum of those rows' counts, modulo 2^64
+ *   The record of base b is upper_bound(d_rec_seq, b) - 1: an empty record
+ *   gets three zeros, of equal entries the last one owns the bases, windows
+ *   before the first entry belong to no record.
+ *   n_records == 0: nothing is done.  n_bases < k: nothing is launched and the
+ *   planes are zero.  nt == 0: the hit and sum planes are zero, the table is
+ *   not read.  An index that does not belong to the table, or keys that are
+ *   not ascending, give wrong counts, never a wild address or an endless loop
+ *   (bounds are clamped to nt; every search runs a step count fixed before it
+ *   starts).
+ *   One block per tile of KMAN_SCREEN_TILE windows.  Per valid window: one
+ *   index pair, floor(log2(bucket rows)) + 1 key reads at most, one count read
+ *   on a hit.  The tile's slice of d_rec_seq is staged in LDS when it has at
+ *   most KMAN_SCREEN_REC_CAP entries and searched in global memory otherwise;
+ *   each (tile, record, plane) adds to d_out with at most one 64-bit atomic.
+ *   Launches are timed under the tag "screen".  Synchronises. */
+#define KMAN_SCREEN_MAX_INDEX_BITS 24
+#define KMAN_SCREEN_TILE 4096
+#define KMAN_SCREEN_REC_CAP 512
+int kman_table_index(kman_ctx *ctx, const uint64_t *d_tkeys, uint64_t nt, uint32_t k, uint32_t index_bits,
+                     uint64_t *d_index);
+int kman_screen_records(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases, uint32_t k, uint32_t flags,
+                        const uint64_t *d_rec_seq, uint64_t n_records, const uint64_t *d_tkeys, const void *d_tcounts,
+                        uint32_t t_count_bytes, uint64_t nt, const uint64_t *d_index, uint32_t index_bits,
+                        uint64_t *d_out);
+
 /* kman_rebase_pos: uniq pos tagged with their source shard (bits 56-63) ->
  *   global pos: (pos & (2^56 - 1)) + (offsets[source] << 1), offsets = the
  *   global base index of each shard's first base (host array, nsrc <= 256).
@@ -684,6 +735,13 @@ int kman_format_uniq_mixed_words(const uint64_t *words, uint64_t stride, const u
 int kman_format_uniq_wide(const uint64_t *hi, const uint64_t *lo, const void *pos, uint32_t pos_bytes, uint64_t n,
                           uint32_t k, const char *names, const uint64_t *name_off, const uint64_t *rec_seq,
                           uint64_t n_records, char *out, size_t cap, size_t *used, int threads);
+
+/* kman_screen_records' three planes (out3: windows, hits, count sum, n_records
+ * u64 each) as text, one "%s\t%llu\t%llu\t%llu\n" line (name, windows, hits,
+ * sum) per record r with keep[r] != 0 (keep == NULL: every record), in input
+ * order. */
+int kman_format_screen(const uint64_t *out3, uint64_t n_records, const uint8_t *keep, const char *names,
+                       const uint64_t *name_off, char *buf, size_t cap, size_t *used, int threads);
 
 /* The same writers on the device: the output text is built in
  * HBM (d_out, 16-byte aligned) from device-resident results, so only the text

@@ -42,6 +42,9 @@ KMAN_FINISH_UNIQ = 2
 KMAN_PARSE_IN_RECORD = 1
 KMAN_FILTER_TILE = 4096  # rows per tile of kman_filter_counts (include/kman.h)
 KMAN_MATCH_TILE = 2048  # merged rows (A + B) per tile of kman_match_counts (include/kman.h)
+KMAN_SCREEN_MAX_INDEX_BITS = 24  # widest prefix index of kman_table_index (include/kman.h)
+KMAN_SCREEN_TILE = 4096  # windows per tile of kman_screen_records (include/kman.h)
+KMAN_SCREEN_REC_CAP = 512  # rec_seq entries of a tile staged in LDS; more: searched in global memory
 KMAN_MATCH_RIGHT = 0
 KMAN_MATCH_LEFT = 1
 KMAN_MATCH_MIN = 2
@@ -214,6 +217,14 @@ SIGNATURES = {
     "kman_match_counts": (
         c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_void_p, c_uint32, c_uint64, c_int,
                 c_void_p, c_uint32],
+    ),
+    "kman_table_index": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p]),
+    "kman_screen_records": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32,
+                c_uint64, c_void_p, c_uint32, c_void_p],
+    ),
+    "kman_format_screen": (
+        c_int, [c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t), c_int],
     ),
     "kman_extract_wide": (
         c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64,

@@ -1837,6 +1837,107 @@ def set_op(dev: Device, a: CountResult, b: CountResult, op: str, counts: Optiona
         free_result(only_b)
 
 
+# ------------------------------------------------- reads against a table (screen)
+
+
+def default_index_bits(n: int, k: int) -> int:
+    """table_index's default width: about 8 rows per bucket on spread keys."""
+    return min(2 * k, N.KMAN_SCREEN_MAX_INDEX_BITS, max(1, (max(int(n), 2) - 1).bit_length() - 3))
+
+
+def _check_index_bits(index_bits: int, k: int) -> int:
+    top = min(2 * k, N.KMAN_SCREEN_MAX_INDEX_BITS)
+    if isinstance(index_bits, bool) or not isinstance(index_bits, (int, np.integer)) or not 1 <= index_bits <= top:
+        raise AssertionError("index_bits must be an integer in [1, %d] for k = %d, got %r" % (top, k, index_bits))
+    return int(index_bits)
+
+
+def table_index(dev: Device, table: CountResult, index_bits: Optional[int] = None) -> DeviceBuffer:
+    """kman_table_index: the prefix index of a key-sorted distinct count table
+    (join_groups(.., "count")), 2^index_bits + 1 u64 words in a fresh device
+    buffer: word p = the rows whose top index_bits key bits are < p.
+    index_bits None: min(2k, 24, max(1, ceil(log2(max(n, 2))) - 3)), about 8
+    rows per bucket on spread keys -- a choice nobody has measured against
+    wider or narrower indexes."""
+    if table.k > MAX_K:
+        raise AssertionError("a table index takes k <= %d (one 64-bit key per k-mer), got %d" % (MAX_K, table.k))
+    bits = default_index_bits(table.n, table.k) if index_bits is None else _check_index_bits(index_bits, table.k)
+    idx = dev.alloc(8 * ((1 << bits) + 1))
+    try:
+        N.check(dev.ctx, N.lib().kman_table_index(dev.ctx, c_void_p(table.ukeys.ptr), table.n, table.k, bits,
+                                                  c_void_p(idx.ptr)), "kman_table_index")
+    except BaseException:
+        idx.free()
+        raise
+    return idx
+
+
+def screen(p: Parsed, table: CountResult, canonical: bool = False, index: Optional[DeviceBuffer] = None,
+           index_bits: Optional[int] = None) -> np.ndarray:
+    """kman_screen_records: for every record of p, (valid k-mer windows, those
+    whose key is a row of `table`, the sum of those rows' counts), k =
+    table.k, as an (n_records, 3) u64 array.  canonical: the windows' keys are
+    min(k-mer, reverse complement), for a table counted that way.  `index`: a
+    table_index(dev, table, index_bits) kept by the caller (index_bits is then
+    the width it was built with; None: the default width); None: built and
+    freed here."""
+    if table.k > MAX_K:
+        raise AssertionError("screen takes k <= %d (one 64-bit key per k-mer), got %d" % (MAX_K, table.k))
+    dev, k, R = p.dev, table.k, int(p.n_records)
+    bits = default_index_bits(table.n, k) if index_bits is None else _check_index_bits(index_bits, k)
+    if R == 0:
+        return np.zeros((0, 3), np.uint64)
+    own = d_rec = d_out = None
+    try:
+        if index is None:
+            index = own = table_index(dev, table, bits)
+        d_rec = dev.alloc(8 * R)
+        dev.upload(d_rec, np.ascontiguousarray(p.rec_seq, dtype=np.uint64))
+        d_out = dev.alloc(24 * R)
+        N.check(dev.ctx, N.lib().kman_screen_records(
+            dev.ctx, c_void_p(p.codes.ptr), p.n_bases, k, N.KMAN_CANONICAL if canonical else 0, c_void_p(d_rec.ptr), R,
+            c_void_p(table.ukeys.ptr), c_void_p(table.counts.ptr), table.count_bytes, table.n, c_void_p(index.ptr),
+            bits, c_void_p(d_out.ptr)), "kman_screen_records")
+        planes = dev.download(d_out, 3 * R, np.uint64)
+    finally:
+        for b in (own, d_rec, d_out):
+            if b is not None:
+                b.free()
+    return np.ascontiguousarray(planes.reshape(3, R).T)
+
+
+def screen_keep(stats: np.ndarray, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False) -> np.ndarray:
+    """Which records of screen()'s rows are written, a u8 mask: those with
+    hits >= min_hits and hits >= min_frac * windows (float64), the others
+    when `invert`."""
+    stats = np.asarray(stats, dtype=np.uint64).reshape(-1, 3)
+    windows, hits = stats[:, 0].astype(np.float64), stats[:, 1].astype(np.float64)
+    keep = (hits >= min_hits) & (hits >= min_frac * windows)
+    if invert:
+        keep = ~keep
+    return keep.astype(np.uint8)
+
+
+def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None):
+    """The `kmer screen` text of screen()'s rows: one "name<TAB>windows<TAB>
+    hits<TAB>sum" line per record with keep != 0 (None: all), in input order
+    (kman_format_screen); returned, or written to the binary file `sink`."""
+    stats = np.asarray(stats, dtype=np.uint64).reshape(-1, 3)
+    R = stats.shape[0]
+    if R != p.n_records:
+        raise AssertionError("%d rows for %d records" % (R, p.n_records))
+    planes = np.ascontiguousarray(stats.T)
+    off = np.ascontiguousarray(p.name_off, dtype=np.uint64)
+    kp = None
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.shape != (R,):
+            raise AssertionError("keep mask of %r for %d records" % (keep.shape, R))
+        kp = keep.ctypes.data_as(c_void_p)
+    return _to(sink, _format(N.lib().kman_format_screen, planes.ctypes.data_as(c_void_p), R, kp, p.names_blob,
+                             off.ctypes.data_as(c_void_p)))
+
+
 def join_groups(p: Parsed, k: int, rc: bool, mode: str, max_keys: Optional[int] = None, canonical: bool = False):
     """The count / uniq result of the whole stream of p on the device, by the
     fastest path that takes it: the region path (kman_groups); the multi-batch

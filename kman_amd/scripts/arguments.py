@@ -133,5 +133,50 @@ def set_counts():
                                            "right | min | max | sum; subtract: left; union: sum (default) | max")
 
 
+def reads_path():
+    return click.argument("reads_path", metavar="READS", type=click.Path(exists=True, file_okay=True, readable=True))
+
+
+def table_input():
+    return click.argument("table_input", metavar="TABLE_INPUT",
+                          type=click.Path(exists=True, file_okay=True, readable=True))
+
+
+def table_min_count():
+    return click.option("--min-count", "-L", "min_count", type=click.IntRange(min=1), default=1,
+                        help="Look up only k-mers seen at least this often in TABLE_INPUT. Default: 1 (all)")
+
+
+def table_max_count():
+    return click.option("--max-count", "-U", "max_count", type=click.IntRange(min=1), default=None,
+                        help="Look up only k-mers seen at most this often in TABLE_INPUT. Default: no limit")
+
+
+def screen_canonical():
+    return click.option("--canonical", "canonical", is_flag=True,
+                        help="Canonical k-mers, min(k-mer, reverse complement), in TABLE_INPUT and in the reads")
+
+
+def min_hits():
+    return click.option("--min-hits", "min_hits", type=click.INT, default=0,
+                        help="Write only records with at least this many k-mers found. Default: 0 (all)")
+
+
+def min_frac():
+    return click.option("--min-frac", "min_frac", type=click.FLOAT, default=0.0,
+                        help="Write only records with at least this fraction (0..1) of their k-mers found. "
+                             "Default: 0.0 (all)")
+
+
+def invert():
+    return click.option("--invert", "-v", "invert", is_flag=True,
+                        help="Write the records that --min-hits / --min-frac leave out instead")
+
+
+def index_bits():
+    return click.option("--index-bits", "index_bits", type=click.IntRange(1, 24), default=None,
+                        help="Key bits of the table's prefix index (at most 2 K). Default: about 8 rows per bucket")
+
+
 def re_sort():
     return click.option("--re-sort", "-R", is_flag=True, help="Force batch re-sorting, when loaded with -B.")

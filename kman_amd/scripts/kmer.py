@@ -2,7 +2,7 @@
 
 Same arguments, flags, defaults, outputs and errors as the reference CLI; the
 work runs on the GPU through kman_amd (FastaBatcher.do + KJoiner.join).
-``hist`` and ``sets`` are this engine's own commands.
+``hist``, ``sets`` and ``screen`` are this engine's own commands.
 """
 
 from __future__ import annotations
@@ -371,6 +371,93 @@ def _check_sets_options(k: int, op: str, counts: Optional[str], reverse: bool, c
     engine.check_set_op(op, counts)
     if max_count is not None and min_count > max_count:
         raise AssertionError("--min-count %d is greater than --max-count %d" % (min_count, max_count))
+
+
+@main.command(name="screen", context_settings=CONTEXT_SETTINGS, help="""
+Per-read k-mer hits against a table: for every record of READS, how many of
+its k-mers occur among the k-mers of TABLE_INPUT, written to OUTPUT as one
+"NAME<TAB>K-MERS<TAB>HITS<TAB>SUM" line per record in input order (SUM: the
+sum over the record's found k-mers of their counts in TABLE_INPUT).
+
+Not part of the reference kman CLI.  TABLE_INPUT is counted on the GPU and
+the reads' k-mers are looked up there (kman_screen_records); neither goes
+through a text file.  READS, TABLE_INPUT: fasta or fastq files, plain or
+gzipped, each detected on its own.  K <= 32.  -L / -U select the k-mers of
+TABLE_INPUT that are looked up; --min-hits / --min-frac / -v the records that
+are written.  Launched one process per GPU, the command runs on rank 0 alone.
+""")
+@args.reads_path()
+@args.table_input()
+@args.output_path(file_okay=True)
+@args.k()
+@args.screen_canonical()
+@args.input_format()
+@args.min_qual()
+@args.phred_offset()
+@args.table_min_count()
+@args.table_max_count()
+@args.min_hits()
+@args.min_frac()
+@args.invert()
+@args.index_bits()
+def screen(reads_path: str, table_input: str, output_path: str, k: int, canonical: bool = False,
+           input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33", min_count: int = 1,
+           max_count: Optional[int] = None, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False,
+           index_bits: Optional[int] = None) -> None:
+    input_file_exists(reads_path)
+    input_file_exists(table_input)
+    fastq = [_is_fastq(p, input_format) for p in (reads_path, table_input)]
+    _check_screen_options(k, min_qual, fastq, min_count, max_count, min_hits, min_frac, index_bits)
+    if launch.distributed() and not launch.solo_rank():
+        launch.log_solo("kmer screen")  # (the table and the reads on one GPU: DESIGN §8)
+        return
+    dev = engine.default_device()
+    table = None
+    try:
+        # (the table input's parse buffers are freed before READS is parsed)
+        p = engine.parse_file(dev, table_input, input_format, min_qual if fastq[1] else 0, int(phred_offset))
+        try:
+            engine.check_empty_names(p, k)
+            table = engine.join_groups(p, k, False, "count", canonical=canonical)
+        finally:
+            p.free()
+        if table is None:
+            table = engine.empty_count(dev, k)  # (no k-mers: the empty table, every read has 0 hits)
+        elif min_count > 1 or max_count is not None:
+            solid = engine.filtered_copy(dev, table, min_count, max_count)
+            engine.free_result(table)
+            table = solid
+        p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset))
+        try:
+            stats = engine.screen(p, table, canonical, index_bits=index_bits)
+            keep = engine.screen_keep(stats, min_hits, min_frac, invert)
+            with open(output_path, "wb") as fh:
+                engine.emit_screen(p, stats, keep, fh)
+        finally:
+            p.free()
+    finally:
+        engine.free_result(table)
+    logging.info("That's all!")
+
+
+def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_count: Optional[int], min_hits: int,
+                          min_frac: float, index_bits: Optional[int]) -> None:
+    """What `kmer screen` refuses, before any device work or output."""
+    if k <= 1:
+        raise AssertionError("k must be >= 1, got %d instead." % k)
+    if k > engine.MAX_K:
+        raise AssertionError("kmer screen takes K <= %d (one 64-bit key per k-mer), got %d: word keys are a stated "
+                             "limit of this command" % (engine.MAX_K, k))
+    if min_qual > 0 and not any(fastq):
+        raise AssertionError("--min-qual needs fastq input: neither READS nor TABLE_INPUT is fastq")
+    if max_count is not None and min_count > max_count:
+        raise AssertionError("--min-count %d is greater than --max-count %d" % (min_count, max_count))
+    if not 0.0 <= min_frac <= 1.0:  # (a NaN is refused too)
+        raise AssertionError("--min-frac must be in [0, 1], got %r" % min_frac)
+    if min_hits < 0:
+        raise AssertionError("--min-hits must be >= 0, got %d" % min_hits)
+    if index_bits is not None and index_bits > 2 * k:
+        raise AssertionError("--index-bits %d is more than the 2 K = %d bits of a k-mer" % (index_bits, 2 * k))
 
 
 if __name__ == "__main__":
