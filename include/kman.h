@@ -685,6 +685,68 @@ int kman_screen_records(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases,
                         uint32_t t_count_bytes, uint64_t nt, const uint64_t *d_index, uint32_t index_bits,
                         uint64_t *d_out);
 
+/* ------------------------------------------- per-record order statistic
+ * Not in the reference: one quantile (the median, by default) of the table
+ * counts of a record's k-mer windows.  A sum commutes and an order statistic
+ * does not, so the per-window counts are written once and a selection runs
+ * inside every record.
+ *
+ * kman_window_counts: the arguments of kman_screen_records without the
+ *   record table and d_out, checked the same way (a refused call writes
+ *   nothing), plus d_wc, 16-byte aligned, room for n_bases u32.  For every
+ *   b < n_bases:
+ *     d_wc[b] = KMAN_WC_NONE   no valid window starts at base b (the windows
+ *                              that kman_screen_records' first plane counts
+ *                              are the others): the last k - 1 bases of a
+ *                              record and of the input; every word when
+ *                              n_bases < k (nothing is launched then)
+ *               otherwise      the count of the window's key (the canonical
+ *                              key under KMAN_CANONICAL) in the table: 0 when
+ *                              it is not a row, 0xFFFFFFFE when a u64 count is
+ *                              larger than that
+ *   Words past n_bases are not written.  One block per tile of
+ *   KMAN_SCREEN_TILE windows, the lookup of kman_screen_records (the same
+ *   device function, the same bounds: a foreign index or unsorted keys give
+ *   wrong counts, never a wild address or an endless loop), a 4 B store per
+ *   base in 16-byte vectors.  Launches are timed under "window_counts".
+ *   Synchronises.
+ *
+ * kman_record_quantile: record r owns bases [d_rec_seq[r], d_rec_seq[r + 1]),
+ *   the last record runs to n_bases; equal neighbours are empty records,
+ *   bases before d_rec_seq[0] belong to nobody, entries are clamped to
+ *   n_bases.  With v_0 <= .. <= v_{w-1} the record's words that are not
+ *   KMAN_WC_NONE, ascending: d_q[r] = v_{floor((w - 1) * num / den)}, and 0
+ *   when w == 0.  1/2 is the lower median, 0/1 the minimum, 1/1 the maximum.
+ *   1 <= den <= 65535 and num <= den, else KMAN_EINVAL with nothing written.
+ *   d_q: n_records u32.  d_wc (16-byte aligned) is scratch afterwards.
+ *   n_records == 0: nothing is done.
+ *   Records of at most KMAN_QUANTILE_REC_CAP bases: a chunk of
+ *   KMAN_QUANTILE_TILE bases owns the records that start in it, stages them
+ *   whole in LDS and a wave per record radix-selects the word (8-bit digits);
+ *   the chunk's slice of d_rec_seq is staged when it has at most
+ *   KMAN_QUANTILE_SLICE records and read from global memory otherwise.
+ *   Longer records are listed, gathered as (slot << 32 | word) keys, sorted
+ *   with kman_sort and picked by rank; this needs work memory:
+ *   kman_record_quantile_plan (host only) gives the bytes for n_long_records
+ *   records longer than KMAN_QUANTILE_REC_CAP bases holding n_long_values
+ *   bases together (0, 0: the size every call needs).  d_work 16-byte aligned.
+ *   A buffer too small for the records met: KMAN_ECAP, no fault (d_q may then
+ *   hold the short records' words already).  An unsorted d_rec_seq gives wrong
+ *   or unwritten words, never a wild address.  Launches are timed under
+ *   "record_quantile" and, the long records' gather and pick,
+ *   "record_quantile_long".  Synchronises. */
+#define KMAN_WC_NONE 0xFFFFFFFFu
+#define KMAN_QUANTILE_TILE 4096
+#define KMAN_QUANTILE_REC_CAP 2048
+#define KMAN_QUANTILE_SLICE 1024
+int kman_window_counts(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases, uint32_t k, uint32_t flags,
+                       const uint64_t *d_tkeys, const void *d_tcounts, uint32_t t_count_bytes, uint64_t nt,
+                       const uint64_t *d_index, uint32_t index_bits, uint32_t *d_wc);
+int kman_record_quantile_plan(uint64_t n_long_records, uint64_t n_long_values, uint64_t *work_bytes);
+int kman_record_quantile(kman_ctx *ctx, uint32_t *d_wc, uint64_t n_bases, const uint64_t *d_rec_seq,
+                         uint64_t n_records, uint32_t num, uint32_t den, void *d_work, uint64_t work_bytes,
+                         uint32_t *d_q);
+
 /* kman_rebase_pos: uniq pos tagged with their source shard (bits 56-63) ->
  *   global pos: (pos & (2^56 - 1)) + (offsets[source] << 1), offsets = the
  *   global base index of each shard's first base (host array, nsrc <= 256).
@@ -742,6 +804,11 @@ int kman_format_uniq_wide(const uint64_t *hi, const uint64_t *lo, const void *po
  * order. */
 int kman_format_screen(const uint64_t *out3, uint64_t n_records, const uint8_t *keep, const char *names,
                        const uint64_t *name_off, char *buf, size_t cap, size_t *used, int threads);
+/* The same with a fifth column: "%s\t%llu\t%llu\t%llu\t%u\n" (name, windows,
+ * hits, sum, median[r]: kman_record_quantile's word of the record). */
+int kman_format_screen_median(const uint64_t *out3, const uint32_t *median, uint64_t n_records, const uint8_t *keep,
+                              const char *names, const uint64_t *name_off, char *buf, size_t cap, size_t *used,
+                              int threads);
 
 /* The same writers on the device: the output text is built in
  * HBM (d_out, 16-byte aligned) from device-resident results, so only the text

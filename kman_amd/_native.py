@@ -45,6 +45,10 @@ KMAN_MATCH_TILE = 2048  # merged rows (A + B) per tile of kman_match_counts (inc
 KMAN_SCREEN_MAX_INDEX_BITS = 24  # widest prefix index of kman_table_index (include/kman.h)
 KMAN_SCREEN_TILE = 4096  # windows per tile of kman_screen_records (include/kman.h)
 KMAN_SCREEN_REC_CAP = 512  # rec_seq entries of a tile staged in LDS; more: searched in global memory
+KMAN_WC_NONE = 0xFFFFFFFF  # kman_window_counts: no valid window starts at this base (include/kman.h)
+KMAN_QUANTILE_TILE = 4096  # bases per chunk of kman_record_quantile (include/kman.h)
+KMAN_QUANTILE_REC_CAP = 2048  # the longest record selected in LDS; longer ones: gathered and sorted
+KMAN_QUANTILE_SLICE = 1024  # records of a chunk whose rec_seq entries are staged in LDS
 KMAN_MATCH_RIGHT = 0
 KMAN_MATCH_LEFT = 1
 KMAN_MATCH_MIN = 2
@@ -225,6 +229,18 @@ SIGNATURES = {
     ),
     "kman_format_screen": (
         c_int, [c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t), c_int],
+    ),
+    "kman_format_screen_median": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t),
+                c_int],
+    ),
+    "kman_window_counts": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p,
+                c_uint32, c_void_p],
+    ),
+    "kman_record_quantile_plan": (c_int, [c_uint64, c_uint64, POINTER(c_uint64)]),
+    "kman_record_quantile": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p],
     ),
     "kman_extract_wide": (
         c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64,

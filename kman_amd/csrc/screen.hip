@@ -43,6 +43,7 @@
 // HBM when the table is larger than the caches), 4 / 8 B of count on a hit.
 #include "common.h"
 #include "kmer.h"
+#include "screen_lookup.h"
 
 namespace {
 
@@ -53,10 +54,6 @@ constexpr int SCAP = KMAN_SCREEN_REC_CAP;
 static_assert(STILE == KMAN_SCREEN_TILE, "include/kman.h states the tile size");
 static_assert(STILE % SCAP == 0, "the global path's rounds tile the offsets");
 
-KMAN_DEV uint64_t smin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
-// halvings that empty a range of len rows: bits(len), 0 for an empty one
-KMAN_DEV uint32_t steps_of(uint64_t len) { return len ? 64u - (uint32_t)__builtin_clzll(len) : 0u; }
 inline uint32_t host_steps_of(uint64_t len) {
     uint32_t s = 0;
     for (; len; len >>= 1) s++;
@@ -134,46 +131,9 @@ __global__ __launch_bounds__(ST) void screen_kernel(const uint8_t *__restrict__ 
     const uint64_t p0 = tb + (uint64_t)threadIdx.x * SEI;
     const uint32_t valid = roll<SEI, CANON>(scodes, threadIdx.x * SEI, k, mask, p0, n_bases, kf, kr);
 
-    // ---- lookup: 16 searches in lockstep
-    uint64_t lo[SEI], len[SEI];
-#pragma unroll
-    for (int j = 0; j < SEI; j++) {
-        const bool ok = (valid >> j) & 1u;
-        const uint64_t p = kf[j] >> shift;
-        lo[j] = ok ? index[p] : 0;
-        len[j] = ok ? index[p + 1] : 0;
-    }
-    uint32_t nsteps = 0;
-#pragma unroll
-    for (int j = 0; j < SEI; j++) {
-        const uint64_t hi = smin64(len[j], nt);  // lo <= hi <= nt whatever the index holds
-        lo[j] = smin64(lo[j], hi);
-        len[j] = hi - lo[j];
-        const uint32_t s = steps_of(len[j]);
-        nsteps = s > nsteps ? s : nsteps;
-    }
-    uint32_t hit = 0;
-    for (uint32_t s = 0; s < nsteps; s++) {  // (nsteps <= 64)
-        uint64_t v[SEI];
-#pragma unroll
-        for (int j = 0; j < SEI; j++) v[j] = len[j] ? tkeys[lo[j] + (len[j] >> 1)] : 0;  // (lo + half < lo + len <= nt)
-#pragma unroll
-        for (int j = 0; j < SEI; j++) {
-            const uint64_t half = len[j] >> 1;
-            const bool on = len[j] != 0;
-            hit |= (uint32_t)(on && v[j] == kf[j]) << j;
-            if (on && v[j] < kf[j]) {
-                lo[j] += half + 1;
-                len[j] -= half + 1;
-            } else {
-                len[j] = half;
-            }
-        }
-    }
-    // a hit's row is where its lower bound ended (lo < nt then)
+    // ---- lookup: 16 searches in lockstep (screen_lookup.h, shared with kman_window_counts)
     uint64_t cnt[SEI];
-#pragma unroll
-    for (int j = 0; j < SEI; j++) cnt[j] = ((hit >> j) & 1u) && lo[j] < nt ? (uint64_t)tcounts[lo[j]] : 0;
+    const uint32_t hit = table_lookup<SEI, CT>(valid, kf, shift, index, tkeys, tcounts, nt, cnt);
 
     // ---- per-record reduction
     const uint64_t *rs = big ? rec_seq + r0 : srec;
@@ -245,11 +205,6 @@ void launch_screen(kman_ctx *ctx, const uint8_t *codes, uint64_t n_bases, uint32
     hipLaunchKernelGGL((screen_kernel<CANON, CT>), dim3((uint32_t)tiles), dim3(ST), 0, ctx->stream, codes, n_bases,
                        (int)k, rec_seq, n_records, tkeys, (const CT *)tcounts, nt, index, shift,
                        (unsigned long long *)out);
-}
-
-bool index_bits_ok(uint32_t k, uint32_t index_bits) {
-    const uint32_t top = 2 * k < KMAN_SCREEN_MAX_INDEX_BITS ? 2 * k : KMAN_SCREEN_MAX_INDEX_BITS;
-    return index_bits >= 1 && index_bits <= top;
 }
 
 }  // namespace

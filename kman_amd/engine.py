@@ -1906,22 +1906,133 @@ def screen(p: Parsed, table: CountResult, canonical: bool = False, index: Option
     return np.ascontiguousarray(planes.reshape(3, R).T)
 
 
-def screen_keep(stats: np.ndarray, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False) -> np.ndarray:
+def window_counts(p: Parsed, table: CountResult, canonical: bool = False, index: Optional[DeviceBuffer] = None,
+                  index_bits: Optional[int] = None) -> DeviceBuffer:
+    """kman_window_counts: one u32 per base of p in a fresh device buffer (the
+    caller frees it): the count in `table` of the k-mer window that starts at
+    that base (0: not a row; counts above 0xFFFFFFFE saturate there),
+    N.KMAN_WC_NONE where no valid window starts.  canonical, index, index_bits
+    as for screen()."""
+    if table.k > MAX_K:
+        raise AssertionError("window_counts takes k <= %d (one 64-bit key per k-mer), got %d" % (MAX_K, table.k))
+    dev, k = p.dev, table.k
+    bits = default_index_bits(table.n, k) if index_bits is None else _check_index_bits(index_bits, k)
+    own = d_wc = None
+    try:
+        if index is None:
+            index = own = table_index(dev, table, bits)
+        d_wc = dev.alloc(max(16, 4 * int(p.n_bases)))
+        N.check(dev.ctx, N.lib().kman_window_counts(
+            dev.ctx, c_void_p(p.codes.ptr), p.n_bases, k, N.KMAN_CANONICAL if canonical else 0,
+            c_void_p(table.ukeys.ptr), c_void_p(table.counts.ptr), table.count_bytes, table.n, c_void_p(index.ptr),
+            bits, c_void_p(d_wc.ptr)), "kman_window_counts")
+        res, d_wc = d_wc, None
+        return res
+    finally:
+        for b in (own, d_wc):
+            if b is not None:
+                b.free()
+
+
+def quantile_plan(rec_seq, n_bases: int):
+    """(records longer than KMAN_QUANTILE_REC_CAP bases, the bases they hold
+    together) of a record table, as kman_record_quantile clamps and cuts it:
+    the arguments of kman_record_quantile_plan."""
+    rs = np.minimum(np.asarray(rec_seq, dtype=np.uint64), np.uint64(n_bases))
+    if rs.size == 0:
+        return 0, 0
+    ends = np.concatenate([rs[1:], np.asarray([n_bases], dtype=np.uint64)])
+    lens = np.where(ends > rs, ends - rs, np.uint64(0))
+    long_ = lens > np.uint64(N.KMAN_QUANTILE_REC_CAP)
+    return int(long_.sum()), int(lens[long_].sum())
+
+
+def record_quantile(p: Parsed, d_wc: DeviceBuffer, num: int = 1, den: int = 2) -> np.ndarray:
+    """kman_record_quantile over window_counts()'s words: per record of p, the
+    word of rank floor((w - 1) * num / den) among its w words that are not
+    KMAN_WC_NONE, ascending (1/2: the lower median, 0/1: the minimum, 1/1: the
+    maximum), 0 for a record without windows; u32, n_records.  d_wc is
+    scratch afterwards (still the caller's to free)."""
+    for v in (num, den):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise AssertionError("quantile %r / %r: integers" % (num, den))
+    if not (1 <= den <= 65535 and 0 <= num <= den):
+        raise AssertionError("quantile %r / %r: 1 <= den <= 65535 and 0 <= num <= den" % (num, den))
+    dev, R = p.dev, int(p.n_records)
+    if R == 0:
+        return np.zeros(0, np.uint32)
+    rec_seq = np.ascontiguousarray(p.rec_seq, dtype=np.uint64)
+    n_long, n_values = quantile_plan(rec_seq, int(p.n_bases))
+    need = c_uint64(0)
+    N.check(dev.ctx, N.lib().kman_record_quantile_plan(n_long, n_values, byref(need)), "kman_record_quantile_plan")
+    d_rec = d_work = d_q = None
+    try:
+        d_rec = dev.alloc(8 * R)
+        dev.upload(d_rec, rec_seq)
+        d_work = dev.alloc(need.value)
+        d_q = dev.alloc(max(16, 4 * R))
+        N.check(dev.ctx, N.lib().kman_record_quantile(
+            dev.ctx, c_void_p(d_wc.ptr), p.n_bases, c_void_p(d_rec.ptr), R, int(num), int(den), c_void_p(d_work.ptr),
+            need.value, c_void_p(d_q.ptr)), "kman_record_quantile")
+        return dev.download(d_q, R, np.uint32)
+    finally:
+        for b in (d_rec, d_work, d_q):
+            if b is not None:
+                b.free()
+
+
+def screen_median(p: Parsed, table: CountResult, canonical: bool = False, index: Optional[DeviceBuffer] = None,
+                  index_bits: Optional[int] = None, num: int = 1, den: int = 2):
+    """(stats, median): screen()'s rows, from kman_screen_records exactly as
+    screen() gets them, and record_quantile(num, den) of the records' window
+    counts (u32, n_records).  The table's index is built once (or taken from
+    the caller) and used by both kernels."""
+    if table.k > MAX_K:
+        raise AssertionError("screen takes k <= %d (one 64-bit key per k-mer), got %d" % (MAX_K, table.k))
+    bits = default_index_bits(table.n, table.k) if index_bits is None else _check_index_bits(index_bits, table.k)
+    own = d_wc = None
+    try:
+        if index is None:
+            index = own = table_index(p.dev, table, bits)
+        stats = screen(p, table, canonical, index=index, index_bits=bits)
+        d_wc = window_counts(p, table, canonical, index=index, index_bits=bits)
+        return stats, record_quantile(p, d_wc, num, den)
+    finally:
+        for b in (own, d_wc):
+            if b is not None:
+                b.free()
+
+
+def screen_keep(stats: np.ndarray, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False, *, median=None,
+                min_median: Optional[int] = None, max_median: Optional[int] = None) -> np.ndarray:
     """Which records of screen()'s rows are written, a u8 mask: those with
-    hits >= min_hits and hits >= min_frac * windows (float64), the others
-    when `invert`."""
+    hits >= min_hits and hits >= min_frac * windows (float64) and, with
+    `median` (screen_median()'s second result), min_median <= median <=
+    max_median (each bound only when given), the others when `invert`."""
     stats = np.asarray(stats, dtype=np.uint64).reshape(-1, 3)
     windows, hits = stats[:, 0].astype(np.float64), stats[:, 1].astype(np.float64)
     keep = (hits >= min_hits) & (hits >= min_frac * windows)
+    if min_median is not None or max_median is not None:
+        if median is None:
+            raise AssertionError("min_median / max_median need the median array")
+        med = np.asarray(median, dtype=np.uint32).reshape(-1).astype(np.int64)
+        if med.shape[0] != stats.shape[0]:
+            raise AssertionError("%d medians for %d records" % (med.shape[0], stats.shape[0]))
+        if min_median is not None:
+            keep &= med >= min(int(min_median), 1 << 40)  # (bounds outside u32 clipped into int64)
+        if max_median is not None:
+            keep &= med <= max(int(max_median), -1)
     if invert:
         keep = ~keep
     return keep.astype(np.uint8)
 
 
-def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None):
+def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None, median=None):
     """The `kmer screen` text of screen()'s rows: one "name<TAB>windows<TAB>
     hits<TAB>sum" line per record with keep != 0 (None: all), in input order
-    (kman_format_screen); returned, or written to the binary file `sink`."""
+    (kman_format_screen); with `median` (u32 per record) a fifth column
+    "<TAB>median" (kman_format_screen_median).  Returned, or written to the
+    binary file `sink`."""
     stats = np.asarray(stats, dtype=np.uint64).reshape(-1, 3)
     R = stats.shape[0]
     if R != p.n_records:
@@ -1934,6 +2045,12 @@ def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None):
         if keep.shape != (R,):
             raise AssertionError("keep mask of %r for %d records" % (keep.shape, R))
         kp = keep.ctypes.data_as(c_void_p)
+    if median is not None:
+        median = np.ascontiguousarray(median, dtype=np.uint32)
+        if median.shape != (R,):
+            raise AssertionError("median array of %r for %d records" % (median.shape, R))
+        return _to(sink, _format(N.lib().kman_format_screen_median, planes.ctypes.data_as(c_void_p),
+                                 median.ctypes.data_as(c_void_p), R, kp, p.names_blob, off.ctypes.data_as(c_void_p)))
     return _to(sink, _format(N.lib().kman_format_screen, planes.ctypes.data_as(c_void_p), R, kp, p.names_blob,
                              off.ctypes.data_as(c_void_p)))
 

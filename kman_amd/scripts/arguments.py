@@ -173,6 +173,22 @@ def invert():
                         help="Write the records that --min-hits / --min-frac leave out instead")
 
 
+def median():
+    return click.option("--median", "median", is_flag=True,
+                        help="Write a fifth column: the median count in TABLE_INPUT over the record's k-mers "
+                             "(absent k-mers count 0; the lower median; 0 for a record without k-mers)")
+
+
+def min_median():
+    return click.option("--min-median", "min_median", type=click.INT, default=None,
+                        help="Write only records whose median is at least this (>= 0). Implies --median")
+
+
+def max_median():
+    return click.option("--max-median", "max_median", type=click.INT, default=None,
+                        help="Write only records whose median is at most this (>= 0). Implies --median")
+
+
 def index_bits():
     return click.option("--index-bits", "index_bits", type=click.IntRange(1, 24), default=None,
                         help="Key bits of the table's prefix index (at most 2 K). Default: about 8 rows per bucket")

@@ -384,7 +384,14 @@ the reads' k-mers are looked up there (kman_screen_records); neither goes
 through a text file.  READS, TABLE_INPUT: fasta or fastq files, plain or
 gzipped, each detected on its own.  K <= 32.  -L / -U select the k-mers of
 TABLE_INPUT that are looked up; --min-hits / --min-frac / -v the records that
-are written.  Launched one process per GPU, the command runs on rank 0 alone.
+are written.  --median adds a fifth column "<TAB>MEDIAN": the median over the
+record's k-mers of their counts in TABLE_INPUT (0 for a k-mer that is not
+there), selected on the GPU (kman_window_counts, kman_record_quantile); counts
+above 4294967294 enter it as 4294967294.  --min-median / --max-median select
+records by it and imply --median; a record without k-mers has median 0.
+Screened against itself (READS = TABLE_INPUT, --canonical) the median is the
+read's coverage estimate.  Launched one process per GPU, the command runs on
+rank 0 alone.
 """)
 @args.reads_path()
 @args.table_input()
@@ -399,15 +406,21 @@ are written.  Launched one process per GPU, the command runs on rank 0 alone.
 @args.min_hits()
 @args.min_frac()
 @args.invert()
+@args.median()
+@args.min_median()
+@args.max_median()
 @args.index_bits()
 def screen(reads_path: str, table_input: str, output_path: str, k: int, canonical: bool = False,
            input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33", min_count: int = 1,
            max_count: Optional[int] = None, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False,
-           index_bits: Optional[int] = None) -> None:
+           index_bits: Optional[int] = None, median: bool = False, min_median: Optional[int] = None,
+           max_median: Optional[int] = None) -> None:
     input_file_exists(reads_path)
     input_file_exists(table_input)
     fastq = [_is_fastq(p, input_format) for p in (reads_path, table_input)]
-    _check_screen_options(k, min_qual, fastq, min_count, max_count, min_hits, min_frac, index_bits)
+    _check_screen_options(k, min_qual, fastq, min_count, max_count, min_hits, min_frac, index_bits, min_median,
+                          max_median)
+    median = median or min_median is not None or max_median is not None
     if launch.distributed() and not launch.solo_rank():
         launch.log_solo("kmer screen")  # (the table and the reads on one GPU: DESIGN §8)
         return
@@ -429,10 +442,15 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
             table = solid
         p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset))
         try:
-            stats = engine.screen(p, table, canonical, index_bits=index_bits)
-            keep = engine.screen_keep(stats, min_hits, min_frac, invert)
+            if median:
+                stats, med = engine.screen_median(p, table, canonical, index_bits=index_bits)
+                keep = engine.screen_keep(stats, min_hits, min_frac, invert, median=med, min_median=min_median,
+                                          max_median=max_median)
+            else:  # (no new kernel, today's bytes)
+                stats, med = engine.screen(p, table, canonical, index_bits=index_bits), None
+                keep = engine.screen_keep(stats, min_hits, min_frac, invert)
             with open(output_path, "wb") as fh:
-                engine.emit_screen(p, stats, keep, fh)
+                engine.emit_screen(p, stats, keep, fh, median=med)
         finally:
             p.free()
     finally:
@@ -441,7 +459,8 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
 
 
 def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_count: Optional[int], min_hits: int,
-                          min_frac: float, index_bits: Optional[int]) -> None:
+                          min_frac: float, index_bits: Optional[int], min_median: Optional[int] = None,
+                          max_median: Optional[int] = None) -> None:
     """What `kmer screen` refuses, before any device work or output."""
     if k <= 1:
         raise AssertionError("k must be >= 1, got %d instead." % k)
@@ -458,6 +477,11 @@ def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_coun
         raise AssertionError("--min-hits must be >= 0, got %d" % min_hits)
     if index_bits is not None and index_bits > 2 * k:
         raise AssertionError("--index-bits %d is more than the 2 K = %d bits of a k-mer" % (index_bits, 2 * k))
+    for name, v in (("--min-median", min_median), ("--max-median", max_median)):
+        if v is not None and v < 0:
+            raise AssertionError("%s must be >= 0, got %d" % (name, v))
+    if min_median is not None and max_median is not None and min_median > max_median:
+        raise AssertionError("--min-median %d is greater than --max-median %d" % (min_median, max_median))
 
 
 if __name__ == "__main__":
