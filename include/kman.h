@@ -747,6 +747,56 @@ int kman_record_quantile(kman_ctx *ctx, uint32_t *d_wc, uint64_t n_bases, const 
                          uint64_t n_records, uint32_t num, uint32_t den, void *d_work, uint64_t work_bytes,
                          uint32_t *d_q);
 
+/* ------------------------------------------- per-record longest solid run
+ * Not in the reference: where in a record the trusted k-mers are.  Over
+ * kman_window_counts' words, base b is SOLID when d_wc[b] != KMAN_WC_NONE and
+ * d_wc[b] >= min_count.  A RUN of record r is a maximal interval of solid
+ * bases inside r's range: it is cut at the record's ends even when the
+ * neighbouring record's words are solid (hand-built words need not have the
+ * KMAN_WC_NONE gap that kman_window_counts leaves before every record start).
+ *
+ * kman_record_runs: d_wc, n_bases u32 as kman_window_counts writes them
+ *   (16-byte aligned); the call does NOT modify them (kman_record_quantile
+ *   leaves them as scratch: on one buffer, runs go first).  Record ownership
+ *   is kman_record_quantile's: record r owns bases [d_rec_seq[r],
+ *   d_rec_seq[r + 1]), the last record runs to n_bases; entries are clamped to
+ *   n_bases; bases before d_rec_seq[0] belong to nobody; of equal entries the
+ *   last one owns the bases, the others are empty records.
+ *   d_out, two planes of n_records u64, zeroed by the call itself:
+ *     d_out[r]              start: the offset from d_rec_seq[r] of the
+ *                           leftmost run of that length
+ *     d_out[n_records + r]  len: the length, in windows, of r's longest run
+ *   Both are 0 when r has no solid base or is empty.
+ *   1 <= min_count <= 0xFFFFFFFE, else KMAN_EINVAL; a NULL pointer with
+ *   non-zero sizes: KMAN_EINVAL; work_bytes below kman_record_runs_plan's
+ *   (host only; d_work 16-byte aligned): KMAN_ECAP.  A refused call writes
+ *   nothing.  n_records == 0: nothing is done.  n_bases == 0: both planes are
+ *   zero, nothing else is launched, d_wc and d_work may be NULL.
+ *   Tiles of KMAN_RUNS_TILE bases, 256 threads, 16 consecutive words per
+ *   thread.  Pass 1 writes 1 + the position of each tile's last non-solid base
+ *   (read from the tile's end, it stops at the first quarter that holds one);
+ *   one block max-scans those words over the tiles; pass 2 reads the tile
+ *   again: a run starts at the larger of that carried position and its
+ *   record's first base, and at a run's end its length is known.  The tile's
+ *   slice of d_rec_seq is staged in LDS when it has at most KMAN_RUNS_REC_CAP
+ *   entries and searched in global memory otherwise.  Runs are reduced in LDS
+ *   per (tile, record); a record inside one tile is stored directly, one that
+ *   reaches out of its tile (at most two per tile) takes one 64-bit atomic max
+ *   on len and, from a last kernel over the tiles' candidates, one 64-bit
+ *   atomic min on start among those that reach it: the same bytes on every
+ *   call.  The words are read at most twice (8 B per base), 16 B are written
+ *   per record, 56 B of work memory per tile.
+ *   An unsorted d_rec_seq gives wrong or unwritten words, never a wild address
+ *   or an unbounded loop: every record index comes from a search over at most
+ *   n_records entries and is checked against n_records, every LDS index
+ *   against its region.  Launches are timed under "record_runs".
+ *   Synchronises. */
+#define KMAN_RUNS_TILE 4096
+#define KMAN_RUNS_REC_CAP 512
+int kman_record_runs_plan(uint64_t n_bases, uint64_t n_records, uint64_t *work_bytes);
+int kman_record_runs(kman_ctx *ctx, const void *d_wc, uint64_t n_bases, const void *d_rec_seq, uint64_t n_records,
+                     uint32_t min_count, void *d_work, uint64_t work_bytes, void *d_out);
+
 /* kman_rebase_pos: uniq pos tagged with their source shard (bits 56-63) ->
  *   global pos: (pos & (2^56 - 1)) + (offsets[source] << 1), offsets = the
  *   global base index of each shard's first base (host array, nsrc <= 256).
@@ -809,6 +859,17 @@ int kman_format_screen(const uint64_t *out3, uint64_t n_records, const uint8_t *
 int kman_format_screen_median(const uint64_t *out3, const uint32_t *median, uint64_t n_records, const uint8_t *keep,
                               const char *names, const uint64_t *name_off, char *buf, size_t cap, size_t *used,
                               int threads);
+/* The same with the record's solid span as two last columns (`kmer screen
+ * --solid`): "%s\t%llu\t%llu\t%llu[\t%u]\t%llu\t%llu\n" (name, windows, hits,
+ * sum, median[r] unless median == NULL, start[r], end[r]). */
+int kman_format_screen_solid(const uint64_t *out3, const uint32_t *median, const uint64_t *start, const uint64_t *end,
+                             uint64_t n_records, const uint8_t *keep, const char *names, const uint64_t *name_off,
+                             char *buf, size_t cap, size_t *used, int threads);
+/* BED lines "%s\t%llu\t%llu\n" (name, start[r], end[r]) for every record r
+ * with keep[r] != 0 (keep == NULL: every record) and end[r] > start[r], in
+ * input order. */
+int kman_format_bed(const uint64_t *start, const uint64_t *end, uint64_t n_records, const uint8_t *keep,
+                    const char *names, const uint64_t *name_off, char *buf, size_t cap, size_t *used, int threads);
 
 /* The same writers on the device: the output text is built in
  * HBM (d_out, 16-byte aligned) from device-resident results, so only the text

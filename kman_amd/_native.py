@@ -49,6 +49,8 @@ KMAN_WC_NONE = 0xFFFFFFFF  # kman_window_counts: no valid window starts at this 
 KMAN_QUANTILE_TILE = 4096  # bases per chunk of kman_record_quantile (include/kman.h)
 KMAN_QUANTILE_REC_CAP = 2048  # the longest record selected in LDS; longer ones: gathered and sorted
 KMAN_QUANTILE_SLICE = 1024  # records of a chunk whose rec_seq entries are staged in LDS
+KMAN_RUNS_TILE = 4096  # bases per tile of kman_record_runs (include/kman.h)
+KMAN_RUNS_REC_CAP = 512  # rec_seq entries of a tile staged in LDS; more: searched in global memory
 KMAN_MATCH_RIGHT = 0
 KMAN_MATCH_LEFT = 1
 KMAN_MATCH_MIN = 2
@@ -241,6 +243,18 @@ SIGNATURES = {
     "kman_record_quantile_plan": (c_int, [c_uint64, c_uint64, POINTER(c_uint64)]),
     "kman_record_quantile": (
         c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p],
+    ),
+    "kman_record_runs_plan": (c_int, [c_uint64, c_uint64, POINTER(c_uint64)]),
+    "kman_record_runs": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_uint32, c_void_p, c_uint64, c_void_p],
+    ),
+    "kman_format_screen_solid": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p, c_size_t,
+                POINTER(c_size_t), c_int],
+    ),
+    "kman_format_bed": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t),
+                c_int],
     ),
     "kman_extract_wide": (
         c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64,

@@ -344,6 +344,70 @@ extern "C" int kman_format_screen_median(const uint64_t *out3, const uint32_t *m
     return run_sliced(n_records, buf, cap, used, threads, size_of, write_at);
 }
 
+// the same lines with the record's solid span as two last columns, after the
+// median when there is one (`kmer screen --solid`)
+extern "C" int kman_format_screen_solid(const uint64_t *out3, const uint32_t *median, const uint64_t *start,
+                                        const uint64_t *end, uint64_t n_records, const uint8_t *keep,
+                                        const char *names, const uint64_t *name_off, char *buf, size_t cap,
+                                        size_t *used, int threads) {
+    if (!used || (n_records && (!out3 || !start || !end || !name_off))) return KMAN_EINVAL;
+    const uint64_t *w = out3, *h = out3 + n_records, *s = out3 + 2 * n_records;
+    auto size_of = [&](uint64_t r) -> size_t {
+        if (keep && !keep[r]) return 0;
+        return (name_off[r + 1] - name_off[r]) + 6 + ndigits(w[r]) + ndigits(h[r]) + ndigits(s[r]) +
+               (median ? 1 + ndigits(median[r]) : 0) + ndigits(start[r]) + ndigits(end[r]);
+    };
+    auto write_at = [&](uint64_t r, char *p) -> char * {
+        if (keep && !keep[r]) return p;
+        const uint64_t L = name_off[r + 1] - name_off[r];
+        if (L) memcpy(p, names + name_off[r], L);
+        p += L;
+        *p++ = '\t';
+        p = put_u64(p, w[r]);
+        *p++ = '\t';
+        p = put_u64(p, h[r]);
+        *p++ = '\t';
+        p = put_u64(p, s[r]);
+        if (median) {
+            *p++ = '\t';
+            p = put_u64(p, median[r]);
+        }
+        *p++ = '\t';
+        p = put_u64(p, start[r]);
+        *p++ = '\t';
+        p = put_u64(p, end[r]);
+        *p++ = '\n';
+        return p;
+    };
+    return run_sliced(n_records, buf, cap, used, threads, size_of, write_at);
+}
+
+// "%s\t%d\t%d\n" % (name, start, end) per kept record with end > start: the
+// BED of the solid spans (`kmer screen --solid C --bed FILE`)
+extern "C" int kman_format_bed(const uint64_t *start, const uint64_t *end, uint64_t n_records, const uint8_t *keep,
+                               const char *names, const uint64_t *name_off, char *buf, size_t cap, size_t *used,
+                               int threads) {
+    if (!used || (n_records && (!start || !end || !name_off))) return KMAN_EINVAL;
+    auto listed = [&](uint64_t r) -> bool { return (!keep || keep[r]) && end[r] > start[r]; };
+    auto size_of = [&](uint64_t r) -> size_t {
+        if (!listed(r)) return 0;
+        return (name_off[r + 1] - name_off[r]) + 3 + ndigits(start[r]) + ndigits(end[r]);
+    };
+    auto write_at = [&](uint64_t r, char *p) -> char * {
+        if (!listed(r)) return p;
+        const uint64_t L = name_off[r + 1] - name_off[r];
+        if (L) memcpy(p, names + name_off[r], L);
+        p += L;
+        *p++ = '\t';
+        p = put_u64(p, start[r]);
+        *p++ = '\t';
+        p = put_u64(p, end[r]);
+        *p++ = '\n';
+        return p;
+    };
+    return run_sliced(n_records, buf, cap, used, threads, size_of, write_at);
+}
+
 // k in 33..64: keys as (hi, lo) word pairs (kman_extract_wide)
 extern "C" int kman_format_count_wide(const uint64_t *hi, const uint64_t *lo, const void *counts, uint32_t count_bytes,
                                       uint64_t n, uint32_t k, char *out, size_t cap, size_t *used, int threads) {

@@ -2003,12 +2003,96 @@ def screen_median(p: Parsed, table: CountResult, canonical: bool = False, index:
                 b.free()
 
 
+def _check_min_count(min_count) -> int:
+    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or \
+            not 1 <= min_count <= N.KMAN_WC_NONE - 1:
+        raise AssertionError("min_count must be an integer in [1, %d], got %r" % (N.KMAN_WC_NONE - 1, min_count))
+    return int(min_count)
+
+
+def record_runs(p: Parsed, d_wc: DeviceBuffer, min_count: int) -> np.ndarray:
+    """kman_record_runs over window_counts()'s words: per record of p, (start,
+    len) of its longest run of solid bases (word != KMAN_WC_NONE and >=
+    min_count): len in windows, start the offset from the record's first base
+    of the leftmost run of that length, both 0 for a record without a solid
+    base; an (n_records, 2) u64 array.  d_wc is not modified."""
+    min_count = _check_min_count(min_count)
+    dev, R = p.dev, int(p.n_records)
+    if R == 0:
+        return np.zeros((0, 2), np.uint64)
+    need = c_uint64(0)
+    N.check(dev.ctx, N.lib().kman_record_runs_plan(int(p.n_bases), R, byref(need)), "kman_record_runs_plan")
+    d_rec = d_work = d_out = None
+    try:
+        d_rec = dev.alloc(8 * R)
+        dev.upload(d_rec, np.ascontiguousarray(p.rec_seq, dtype=np.uint64))
+        d_work = dev.alloc(need.value)
+        d_out = dev.alloc(16 * R)
+        N.check(dev.ctx, N.lib().kman_record_runs(
+            dev.ctx, c_void_p(d_wc.ptr), p.n_bases, c_void_p(d_rec.ptr), R, min_count, c_void_p(d_work.ptr),
+            need.value, c_void_p(d_out.ptr)), "kman_record_runs")
+        planes = dev.download(d_out, 2 * R, np.uint64)
+    finally:
+        for b in (d_rec, d_work, d_out):
+            if b is not None:
+                b.free()
+    return np.ascontiguousarray(planes.reshape(2, R).T)
+
+
+def solid_spans(runs, k: int):
+    """(START, END) of record_runs()'s rows in bases within the record, as
+    `codes` holds them (every sequence character counts, N included; line
+    breaks do not): START = start, END = start + len + k - 1 where len > 0 (a
+    run of len windows covers len + k - 1 bases), both 0 otherwise."""
+    runs = np.asarray(runs, dtype=np.uint64).reshape(-1, 2)
+    has = runs[:, 1] > 0
+    start = np.where(has, runs[:, 0], np.uint64(0)).astype(np.uint64)
+    end = np.where(has, runs[:, 0] + runs[:, 1] + np.uint64(int(k) - 1), np.uint64(0)).astype(np.uint64)
+    return np.ascontiguousarray(start), np.ascontiguousarray(end)
+
+
+def screen_solid(p: Parsed, table: CountResult, canonical: bool, min_count: int, *, median: bool = False,
+                 index: Optional[DeviceBuffer] = None, index_bits: Optional[int] = None):
+    """(stats, median or None, runs): screen()'s rows, record_quantile()'s
+    lower median when `median`, and record_runs(min_count) of the records'
+    window counts.  The table's index is built once (or taken from the caller)
+    and serves every kernel; window_counts runs once, and the runs are taken
+    before the quantile, which leaves the words as scratch."""
+    if table.k > MAX_K:
+        raise AssertionError("screen takes k <= %d (one 64-bit key per k-mer), got %d" % (MAX_K, table.k))
+    min_count = _check_min_count(min_count)
+    bits = default_index_bits(table.n, table.k) if index_bits is None else _check_index_bits(index_bits, table.k)
+    own = d_wc = None
+    try:
+        if index is None:
+            index = own = table_index(p.dev, table, bits)
+        stats = screen(p, table, canonical, index=index, index_bits=bits)
+        d_wc = window_counts(p, table, canonical, index=index, index_bits=bits)
+        runs = record_runs(p, d_wc, min_count)
+        med = record_quantile(p, d_wc) if median else None
+        return stats, med, runs
+    finally:
+        for b in (own, d_wc):
+            if b is not None:
+                b.free()
+
+
+def _span_arrays(span, R: int):
+    start, end = (np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1)) for a in span)
+    if start.shape != (R,) or end.shape != (R,):
+        raise AssertionError("span arrays of %r and %r for %d records" % (start.shape, end.shape, R))
+    return start, end
+
+
 def screen_keep(stats: np.ndarray, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False, *, median=None,
-                min_median: Optional[int] = None, max_median: Optional[int] = None) -> np.ndarray:
+                min_median: Optional[int] = None, max_median: Optional[int] = None, span=None,
+                min_solid_len: Optional[int] = None) -> np.ndarray:
     """Which records of screen()'s rows are written, a u8 mask: those with
     hits >= min_hits and hits >= min_frac * windows (float64) and, with
     `median` (screen_median()'s second result), min_median <= median <=
-    max_median (each bound only when given), the others when `invert`."""
+    max_median (each bound only when given) and, with `span` (solid_spans()'s
+    pair), END - START >= min_solid_len (when given), the others when
+    `invert`."""
     stats = np.asarray(stats, dtype=np.uint64).reshape(-1, 3)
     windows, hits = stats[:, 0].astype(np.float64), stats[:, 1].astype(np.float64)
     keep = (hits >= min_hits) & (hits >= min_frac * windows)
@@ -2022,17 +2106,23 @@ def screen_keep(stats: np.ndarray, min_hits: int = 0, min_frac: float = 0.0, inv
             keep &= med >= min(int(min_median), 1 << 40)  # (bounds outside u32 clipped into int64)
         if max_median is not None:
             keep &= med <= max(int(max_median), -1)
+    if min_solid_len is not None:
+        if span is None:
+            raise AssertionError("min_solid_len needs the span arrays")
+        start, end = _span_arrays(span, stats.shape[0])
+        keep &= (end - np.minimum(start, end)).astype(np.float64) >= float(min_solid_len)
     if invert:
         keep = ~keep
     return keep.astype(np.uint8)
 
 
-def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None, median=None):
+def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None, median=None, *, span=None):
     """The `kmer screen` text of screen()'s rows: one "name<TAB>windows<TAB>
     hits<TAB>sum" line per record with keep != 0 (None: all), in input order
     (kman_format_screen); with `median` (u32 per record) a fifth column
-    "<TAB>median" (kman_format_screen_median).  Returned, or written to the
-    binary file `sink`."""
+    "<TAB>median" (kman_format_screen_median); with `span` (solid_spans()'s
+    pair) two last columns "<TAB>START<TAB>END" (kman_format_screen_solid).
+    Returned, or written to the binary file `sink`."""
     stats = np.asarray(stats, dtype=np.uint64).reshape(-1, 3)
     R = stats.shape[0]
     if R != p.n_records:
@@ -2049,10 +2139,34 @@ def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None, median=None):
         median = np.ascontiguousarray(median, dtype=np.uint32)
         if median.shape != (R,):
             raise AssertionError("median array of %r for %d records" % (median.shape, R))
+    if span is not None:
+        start, end = _span_arrays(span, R)
+        mp = median.ctypes.data_as(c_void_p) if median is not None else None
+        return _to(sink, _format(N.lib().kman_format_screen_solid, planes.ctypes.data_as(c_void_p), mp,
+                                 start.ctypes.data_as(c_void_p), end.ctypes.data_as(c_void_p), R, kp, p.names_blob,
+                                 off.ctypes.data_as(c_void_p)))
+    if median is not None:
         return _to(sink, _format(N.lib().kman_format_screen_median, planes.ctypes.data_as(c_void_p),
                                  median.ctypes.data_as(c_void_p), R, kp, p.names_blob, off.ctypes.data_as(c_void_p)))
     return _to(sink, _format(N.lib().kman_format_screen, planes.ctypes.data_as(c_void_p), R, kp, p.names_blob,
                              off.ctypes.data_as(c_void_p)))
+
+
+def emit_bed(p: Parsed, span, keep, sink=None):
+    """The BED of the solid spans: one "name<TAB>START<TAB>END" line per
+    record with keep != 0 (None: all) and END > START, in input order
+    (kman_format_bed).  Returned, or written to the binary file `sink`."""
+    R = int(p.n_records)
+    start, end = _span_arrays(span, R)
+    off = np.ascontiguousarray(p.name_off, dtype=np.uint64)
+    kp = None
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.shape != (R,):
+            raise AssertionError("keep mask of %r for %d records" % (keep.shape, R))
+        kp = keep.ctypes.data_as(c_void_p)
+    return _to(sink, _format(N.lib().kman_format_bed, start.ctypes.data_as(c_void_p), end.ctypes.data_as(c_void_p), R,
+                             kp, p.names_blob, off.ctypes.data_as(c_void_p)))
 
 
 def join_groups(p: Parsed, k: int, rc: bool, mode: str, max_keys: Optional[int] = None, canonical: bool = False):

@@ -189,6 +189,27 @@ def max_median():
                         help="Write only records whose median is at most this (>= 0). Implies --median")
 
 
+def solid():
+    return click.option("--solid", "solid", type=click.INT, default=None, metavar="C",
+                        help="Write two last columns START and END: the longest stretch of the record whose k-mers "
+                             "all have a count of at least C (1..4294967294) in TABLE_INPUT, the leftmost of equal "
+                             "ones, in bases within the record (0-based, END exclusive; N counts, line breaks do "
+                             "not); 0 and 0 for a record without such a k-mer")
+
+
+def min_solid_len():
+    return click.option("--min-solid-len", "min_solid_len", type=click.INT, default=None, metavar="N",
+                        help="Write only records whose solid stretch has at least N bases (END - START >= N, N >= 0). "
+                             "Needs --solid")
+
+
+def bed():
+    return click.option("--bed", "bed_path", type=click.Path(dir_okay=False, writable=True), default=None,
+                        metavar="FILE",
+                        help="Also write NAME<TAB>START<TAB>END for the written records that have a solid stretch, "
+                             "in input order, to FILE. Needs --solid")
+
+
 def index_bits():
     return click.option("--index-bits", "index_bits", type=click.IntRange(1, 24), default=None,
                         help="Key bits of the table's prefix index (at most 2 K). Default: about 8 rows per bucket")

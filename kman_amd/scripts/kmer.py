@@ -390,8 +390,17 @@ there), selected on the GPU (kman_window_counts, kman_record_quantile); counts
 above 4294967294 enter it as 4294967294.  --min-median / --max-median select
 records by it and imply --median; a record without k-mers has median 0.
 Screened against itself (READS = TABLE_INPUT, --canonical) the median is the
-read's coverage estimate.  Launched one process per GPU, the command runs on
-rank 0 alone.
+read's coverage estimate.  --solid C adds two last columns "<TAB>START<TAB>END"
+(after MEDIAN when that is there): the longest stretch of the record whose
+k-mers all have a count of at least C in TABLE_INPUT, the leftmost of equal
+ones, found on the GPU (kman_record_runs); one threshold per call.  START and
+END count the record's sequence characters from 0, END exclusive: N and other
+non-ACGT letters count (and end a stretch, as do bases masked by -q), line
+breaks of a multi-line fasta do not; a record without such a k-mer has 0 and 0.
+--min-solid-len N selects records with END - START >= N; --bed FILE also writes
+"NAME<TAB>START<TAB>END" for the written records that have a stretch, the
+regions that e.g. `seqtk subseq` cuts out; both need --solid.  Launched one
+process per GPU, the command runs on rank 0 alone.
 """)
 @args.reads_path()
 @args.table_input()
@@ -409,17 +418,21 @@ rank 0 alone.
 @args.median()
 @args.min_median()
 @args.max_median()
+@args.solid()
+@args.min_solid_len()
+@args.bed()
 @args.index_bits()
 def screen(reads_path: str, table_input: str, output_path: str, k: int, canonical: bool = False,
            input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33", min_count: int = 1,
            max_count: Optional[int] = None, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False,
            index_bits: Optional[int] = None, median: bool = False, min_median: Optional[int] = None,
-           max_median: Optional[int] = None) -> None:
+           max_median: Optional[int] = None, solid: Optional[int] = None, min_solid_len: Optional[int] = None,
+           bed_path: Optional[str] = None) -> None:
     input_file_exists(reads_path)
     input_file_exists(table_input)
     fastq = [_is_fastq(p, input_format) for p in (reads_path, table_input)]
     _check_screen_options(k, min_qual, fastq, min_count, max_count, min_hits, min_frac, index_bits, min_median,
-                          max_median)
+                          max_median, solid, min_solid_len, bed_path)
     median = median or min_median is not None or max_median is not None
     if launch.distributed() and not launch.solo_rank():
         launch.log_solo("kmer screen")  # (the table and the reads on one GPU: DESIGN §8)
@@ -437,12 +450,19 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
         if table is None:
             table = engine.empty_count(dev, k)  # (no k-mers: the empty table, every read has 0 hits)
         elif min_count > 1 or max_count is not None:
-            solid = engine.filtered_copy(dev, table, min_count, max_count)
+            ranged = engine.filtered_copy(dev, table, min_count, max_count)
             engine.free_result(table)
-            table = solid
+            table = ranged
         p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset))
         try:
-            if median:
+            span = None
+            if solid is not None:
+                stats, med, runs = engine.screen_solid(p, table, canonical, solid, median=median,
+                                                       index_bits=index_bits)
+                span = engine.solid_spans(runs, k)
+                keep = engine.screen_keep(stats, min_hits, min_frac, invert, median=med, min_median=min_median,
+                                          max_median=max_median, span=span, min_solid_len=min_solid_len)
+            elif median:
                 stats, med = engine.screen_median(p, table, canonical, index_bits=index_bits)
                 keep = engine.screen_keep(stats, min_hits, min_frac, invert, median=med, min_median=min_median,
                                           max_median=max_median)
@@ -450,7 +470,10 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
                 stats, med = engine.screen(p, table, canonical, index_bits=index_bits), None
                 keep = engine.screen_keep(stats, min_hits, min_frac, invert)
             with open(output_path, "wb") as fh:
-                engine.emit_screen(p, stats, keep, fh, median=med)
+                engine.emit_screen(p, stats, keep, fh, median=med, span=span)
+            if bed_path is not None:
+                with open(bed_path, "wb") as fh:
+                    engine.emit_bed(p, span, keep, fh)
         finally:
             p.free()
     finally:
@@ -460,7 +483,8 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
 
 def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_count: Optional[int], min_hits: int,
                           min_frac: float, index_bits: Optional[int], min_median: Optional[int] = None,
-                          max_median: Optional[int] = None) -> None:
+                          max_median: Optional[int] = None, solid: Optional[int] = None,
+                          min_solid_len: Optional[int] = None, bed_path: Optional[str] = None) -> None:
     """What `kmer screen` refuses, before any device work or output."""
     if k <= 1:
         raise AssertionError("k must be >= 1, got %d instead." % k)
@@ -482,6 +506,15 @@ def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_coun
             raise AssertionError("%s must be >= 0, got %d" % (name, v))
     if min_median is not None and max_median is not None and min_median > max_median:
         raise AssertionError("--min-median %d is greater than --max-median %d" % (min_median, max_median))
+    if solid is not None and not 1 <= solid <= 4294967294:
+        raise AssertionError("--solid must be in [1, 4294967294], got %d" % solid)
+    if min_solid_len is not None:
+        if solid is None:
+            raise AssertionError("--min-solid-len needs --solid")
+        if min_solid_len < 0:
+            raise AssertionError("--min-solid-len must be >= 0, got %d" % min_solid_len)
+    if bed_path is not None and solid is None:
+        raise AssertionError("--bed needs --solid")
 
 
 if __name__ == "__main__":
