@@ -797,6 +797,65 @@ int kman_record_runs_plan(uint64_t n_bases, uint64_t n_records, uint64_t *work_b
 int kman_record_runs(kman_ctx *ctx, const void *d_wc, uint64_t n_bases, const void *d_rec_seq, uint64_t n_records,
                      uint32_t min_count, void *d_work, uint64_t work_bytes, void *d_out);
 
+/* ------------------------------------------------- the listed records' text
+ * Not in the reference: the records of the input text that a screen lists,
+ * written as one text on the device, whole or cut to one column interval, so
+ * that only the text crosses PCIe (`kmer screen --reads-out`, `--trim`).
+ *
+ * kman_cut_records: d_text, n_bytes of input text (16-byte aligned; FASTA or
+ *   FASTQ).  d_rec_off: n_records + 1 byte offsets, record r is the bytes
+ *   [d_rec_off[r], d_rec_off[r + 1]): the parsers' d_rec_hdr followed by
+ *   n_bytes.  The offsets themselves need no alignment.  d_keep: one byte per
+ *   record, a record is written when its byte is not 0 (NULL: every record).
+ *   Without KMAN_CUT_TRIM a written record is its bytes, verbatim, and d_start
+ *   and d_end are NULL.  With it (four-line FASTQ records) they hold one column
+ *   interval [START, END) per record, and with L1..L4 the record's first four
+ *   lines without their terminators ("\n", "\r\n" or a lone "\r" ends a line;
+ *   a line that the record does not have is empty), body = L2 right-stripped
+ *   of " \t\v\f" and the bytes 0x1c..0x1f, cols = the offsets of the bytes of
+ *   body that are not ' ', c0 = cols[START], c1 = cols[END - 1] + 1, the
+ *   record is written as
+ *       L1 "\n" L2[c0, c1) "\n" L3 "\n" L4[c0, c1) "\n"
+ *   (L4 cut like a Python slice: both ends clamped to its length).  These are
+ *   the columns of kman_parse_fastq's codes and of kman_parse_fastq_q's mask.
+ *   The text is the written records' texts in input order.  *used = its size.
+ *   d_out (16-byte aligned) NULL: sizing only, cap is taken as 0.  A text
+ *   larger than cap: KMAN_ECAP, *used is set and d_out is not written at all.
+ *   Records are independent: the slice [i0, i0 + m) of d_keep, d_start and
+ *   d_end with the m + 1 offsets from d_rec_off + i0 gives the matching slice
+ *   of the text.
+ *   flags other than KMAN_CUT_TRIM, d_start or d_end given without
+ *   KMAN_CUT_TRIM, and, with n_records > 0, a NULL d_rec_off or d_work, a NULL
+ *   d_text with n_bytes > 0, a NULL d_start or d_end under KMAN_CUT_TRIM, a
+ *   misaligned d_text, d_out or d_work, or more than 2^31 records: KMAN_EINVAL.
+ *   work_bytes below kman_cut_records_plan's (host only; 16 B per record, 64
+ *   under KMAN_CUT_TRIM, and 16): KMAN_ECAP.  A refused call writes nothing.
+ *   n_records == 0: nothing is launched, *used = 0.  The inputs are never
+ *   modified.
+ *   Bad data gives defined bytes, never a wild address or an unbounded loop:
+ *   every offset is clamped to n_bytes; a record with d_rec_off[r + 1] <=
+ *   d_rec_off[r] writes nothing; under KMAN_CUT_TRIM a record with START >=
+ *   END or START >= len(cols) writes nothing and END is clamped to len(cols);
+ *   every line search ends at the record's end.
+ *   Pass 1 turns every record into segments (source, output length): one
+ *   thread per record, or, under KMAN_CUT_TRIM, one wave per record that walks
+ *   it 1024 bytes at a time (a record of any length: about length / 1024
+ *   steps of that wave).  The lengths are scanned with the decoupled
+ *   look-back.  Pass 2 runs one block per KMAN_CUT_TILE output bytes: its
+ *   slice of the segments is staged in LDS when it has at most
+ *   KMAN_CUT_SEG_CAP of them and searched in global memory otherwise; every
+ *   output word is one 16-byte store, made of two 16-byte text loads and a
+ *   byte shift where it lies inside one segment.  Text bytes are read about
+ *   once, under KMAN_CUT_TRIM lines 1 and 2 twice.  Launches are timed under
+ *   the tag "cut_records".  Synchronises. */
+#define KMAN_CUT_TRIM 1u
+#define KMAN_CUT_TILE 16384
+#define KMAN_CUT_SEG_CAP 1024
+int kman_cut_records_plan(uint64_t n_records, uint32_t flags, uint64_t *work_bytes);
+int kman_cut_records(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_rec_off,
+                     uint64_t n_records, const uint8_t *d_keep, const uint64_t *d_start, const uint64_t *d_end,
+                     uint32_t flags, void *d_work, uint64_t work_bytes, char *d_out, size_t cap, size_t *used);
+
 /* kman_rebase_pos: uniq pos tagged with their source shard (bits 56-63) ->
  *   global pos: (pos & (2^56 - 1)) + (offsets[source] << 1), offsets = the
  *   global base index of each shard's first base (host array, nsrc <= 256).

@@ -51,6 +51,9 @@ KMAN_QUANTILE_REC_CAP = 2048  # the longest record selected in LDS; longer ones:
 KMAN_QUANTILE_SLICE = 1024  # records of a chunk whose rec_seq entries are staged in LDS
 KMAN_RUNS_TILE = 4096  # bases per tile of kman_record_runs (include/kman.h)
 KMAN_RUNS_REC_CAP = 512  # rec_seq entries of a tile staged in LDS; more: searched in global memory
+KMAN_CUT_TRIM = 1  # kman_cut_records: cut every record to its column interval (include/kman.h)
+KMAN_CUT_TILE = 16384  # output bytes per block of kman_cut_records' copy pass
+KMAN_CUT_SEG_CAP = 1024  # segments of a tile staged in LDS; more: searched in global memory
 KMAN_MATCH_RIGHT = 0
 KMAN_MATCH_LEFT = 1
 KMAN_MATCH_MIN = 2
@@ -255,6 +258,11 @@ SIGNATURES = {
     "kman_format_bed": (
         c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t),
                 c_int],
+    ),
+    "kman_cut_records_plan": (c_int, [c_uint64, c_uint32, POINTER(c_uint64)]),
+    "kman_cut_records": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p,
+                c_uint64, c_void_p, c_size_t, POINTER(c_size_t)],
     ),
     "kman_extract_wide": (
         c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64,

@@ -200,12 +200,17 @@ class Parsed:
     names_blob: bytes
     name_off: np.ndarray  # u64, len n_records + 1
     n_masked: int = 0  # FASTQ with a quality threshold: the kept bytes below it (their codes read as N)
+    text: Optional[DeviceBuffer] = None  # the input text on the device (text_bytes + 64), only with keep_text=True
+    text_bytes: int = 0
 
     def record_of(self, base: int) -> int:
         return int(np.searchsorted(self.rec_seq, base, side="right")) - 1
 
     def free(self) -> None:
         self.codes.free()
+        if self.text is not None:
+            self.text.free()
+            self.text = None
 
 
 FORMATS = ("auto", "fasta", "fastq")
@@ -391,13 +396,16 @@ def _call_parse_fastq(dev: Device, d_text, n: int, codes, d_hdr, d_seq, cap: int
     return int(masked.value)
 
 
-def parse_fastq(dev: Device, text: bytes, min_qual: int = 0, phred_offset: int = 33) -> Parsed:
+def parse_fastq(dev: Device, text: bytes, min_qual: int = 0, phred_offset: int = 33, *,
+                keep_text: bool = False) -> Parsed:
     """Four-line FASTQ bytes -> device codes + record table (kman_parse_fastq):
     the same ``Parsed`` as ``parse`` gives for the FASTA of the same records;
     the names follow the record name rule applied to the ``@`` line.  With
     `min_qual` > 0 (0..93) every base whose quality byte is below
     `phred_offset` (33 or 64) + `min_qual` reads as ``N`` (kman_parse_fastq_q);
-    ``Parsed.n_masked`` counts them."""
+    ``Parsed.n_masked`` counts them.  `keep_text`: the device copy of the text
+    is not freed but kept as ``Parsed.text`` (n + 64 more bytes of device
+    memory until ``Parsed.free``), for cut_records."""
     qbyte = _qual_byte(min_qual, phred_offset)
     n = len(text)
     if n == 0:
@@ -423,23 +431,31 @@ def parse_fastq(dev: Device, text: bytes, min_qual: int = 0, phred_offset: int =
             d_seq.free()
     except BaseException:
         codes.free()
+        if keep_text:
+            d_text.free()
         raise
     finally:
-        d_text.free()
+        if not keep_text:
+            d_text.free()
     p = _parsed_fastq(dev, codes, info, rec_hdr, rec_seq, text, n_masked, min_qual)
+    if keep_text:
+        p.text, p.text_bytes = d_text, n
     phases.mark("parse")
     return p
 
 
-def parse(dev: Device, text: bytes, fmt: str = "auto", min_qual: int = 0, phred_offset: int = 33) -> Parsed:
+def parse(dev: Device, text: bytes, fmt: str = "auto", min_qual: int = 0, phred_offset: int = 33, *,
+          keep_text: bool = False) -> Parsed:
     """FASTA bytes -> device codes + record table (kman_parse_fasta); FASTQ
     bytes (`fmt`, ``auto``: sniff_format) go to parse_fastq, with its quality
-    threshold (`min_qual` > 0 needs FASTQ input)."""
+    threshold (`min_qual` > 0 needs FASTQ input).  `keep_text`: the device copy
+    of the text is not freed but kept as ``Parsed.text`` (n + 64 more bytes of
+    device memory until ``Parsed.free``), for cut_records."""
     qbyte = _qual_byte(min_qual, phred_offset)
     fmt = _resolve_format(fmt, lambda at: bytes(text[at:at + (1 << 16)]))
     _check_qual_format(qbyte, fmt)
     if fmt == "fastq":
-        return parse_fastq(dev, text, min_qual, phred_offset)
+        return parse_fastq(dev, text, min_qual, phred_offset, keep_text=keep_text)
     n = len(text)
     if n == 0:
         raise AssertionError("premature end of file or empty file")
@@ -462,17 +478,26 @@ def parse(dev: Device, text: bytes, fmt: str = "auto", min_qual: int = 0, phred_
         rec_seq = dev.download(d_seq, R, np.uint64)
         d_hdr.free()
         d_seq.free()
+    except BaseException:
+        if keep_text:
+            d_text.free()
+        raise
     finally:
-        d_text.free()
+        if not keep_text:
+            d_text.free()
     names = [_title_name(text, int(h)) for h in rec_hdr]
     name_off = np.zeros(R + 1, dtype=np.uint64)
     if R:
         name_off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
     phases.mark("parse")
-    return Parsed(dev, codes, int(info.n_bases), R, rec_hdr, rec_seq, names, b"".join(names), name_off)
+    p = Parsed(dev, codes, int(info.n_bases), R, rec_hdr, rec_seq, names, b"".join(names), name_off)
+    if keep_text:
+        p.text, p.text_bytes = d_text, n
+    return p
 
 
-def parse_file(dev: Device, path: str, fmt: str = "auto", min_qual: int = 0, phred_offset: int = 33) -> Parsed:
+def parse_file(dev: Device, path: str, fmt: str = "auto", min_qual: int = 0, phred_offset: int = 33, *,
+               keep_text: bool = False) -> Parsed:
     """kman_parse_fasta of a FASTA file (batcher.py:480 reads it whole), or
     kman_parse_fastq of a FASTQ file (`fmt`, ``auto``: sniff_format).  A
     plain file is read in _FMT_SLICE chunks straight into two pinned stages,
@@ -480,12 +505,15 @@ def parse_file(dev: Device, path: str, fmt: str = "auto", min_qual: int = 0, phr
     read, so the text crosses host memory once and no pageable copy is made;
     the record names come from the file's header lines (mmap).  Gzip input
     is inflated into memory and parsed from there (read_input + parse).
-    `min_qual`, `phred_offset`: parse_fastq's quality threshold."""
+    `min_qual`, `phred_offset`: parse_fastq's quality threshold.  `keep_text`:
+    the device copy of the (inflated) text is not freed but kept as
+    ``Parsed.text`` (n + 64 more bytes of device memory until ``Parsed.free``),
+    for cut_records."""
     qbyte = _qual_byte(min_qual, phred_offset)
     if path.endswith(".gz"):
         if qbyte and fmt != "fastq":  # (decided from the head, before the whole file is inflated)
             _check_qual_format(qbyte, sniff_file(path) if fmt == "auto" else _resolve_format(fmt, b""))
-        return parse(dev, read_input(path), fmt, min_qual, phred_offset)
+        return parse(dev, read_input(path), fmt, min_qual, phred_offset, keep_text=keep_text)
     import mmap
 
     L = N.lib()
@@ -538,9 +566,12 @@ def parse_file(dev: Device, path: str, fmt: str = "auto", min_qual: int = 0, phr
                 d_seq.free()
         except BaseException:
             codes.free()
+            if keep_text:
+                d_text.free()
             raise
         finally:
-            d_text.free()
+            if not keep_text:
+                d_text.free()
         mm = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
         try:
             if fq:
@@ -548,7 +579,11 @@ def parse_file(dev: Device, path: str, fmt: str = "auto", min_qual: int = 0, phr
                     p = _parsed_fastq(dev, codes, info, rec_hdr, rec_seq, mm, n_masked, min_qual)
                 except BaseException:
                     codes.free()
+                    if keep_text:
+                        d_text.free()
                     raise
+                if keep_text:
+                    p.text, p.text_bytes = d_text, n
                 phases.mark("parse")
                 return p
             names = [_title_name(mm, int(h)) for h in rec_hdr]
@@ -558,7 +593,10 @@ def parse_file(dev: Device, path: str, fmt: str = "auto", min_qual: int = 0, phr
     if R:
         name_off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
     phases.mark("parse")
-    return Parsed(dev, codes, int(info.n_bases), R, rec_hdr, rec_seq, names, b"".join(names), name_off)
+    p = Parsed(dev, codes, int(info.n_bases), R, rec_hdr, rec_seq, names, b"".join(names), name_off)
+    if keep_text:
+        p.text, p.text_bytes = d_text, n
+    return p
 
 
 def check_empty_names(p: Parsed, k: int) -> None:
@@ -1104,7 +1142,7 @@ def _pwrite_target(sink):
         return None, 0
 
 
-def _format_dev(dev: Device, n: int, row_bytes: int, call, sink=None):
+def _format_dev(dev: Device, n: int, row_bytes: int, call, sink=None, *, slices=None):
     """Run a kman_format_*_dev call over row slices.  call(i0, rows, d_out,
     cap, used) formats rows [i0, i0 + rows); row_bytes bounds one row.
     Returns the text (a bytearray), or, with a sink (a binary file), writes
@@ -1116,21 +1154,33 @@ def _format_dev(dev: Device, n: int, row_bytes: int, call, sink=None):
     i - 1 out of the other stage -- pwrite at its file offset, or memmove
     into the result.  (KMAN_FMT_ZC=0: slice i formatted into a device slice
     while slice i - 1 crosses PCIe on the copy stream, kman_copy_d2h_async,
-    and slice i - 2 leaves its stage.)"""
+    and slice i - 2 leaves its stage.)
+
+    `slices`: the caller's own (i0, rows, text bound) per slice, in order, for
+    rows of very different sizes (cut_records); row_bytes is not used then."""
     if n == 0:
         return None if sink is not None else bytearray()
     import concurrent.futures as cf
 
     L = N.lib()
-    rows = max(1, min(n, _FMT_SLICE // max(1, row_bytes)))
-    cap = rows * row_bytes + 16
     used = c_size_t(0)
+    if slices is None:
+        rows = max(1, min(n, _FMT_SLICE // max(1, row_bytes)))
+        cap = rows * row_bytes + 16
+        slices = [(i0, min(rows, n - i0)) for i0 in range(0, n, rows)]
+        sizing = [(0, n)]  # one sizing pass over every row
+    else:
+        cap = max(b for _, _, b in slices) + 16
+        slices = sizing = [(i0, m) for i0, m, _ in slices]
     out, fd, base = None, None, 0
     if sink is None:
-        rc_ = call(0, n, None, 0, used)  # sizing pass over every row
-        if rc_ not in (N.KMAN_OK, N.KMAN_ECAP):
-            N.check(dev.ctx, rc_, "kman_format_*_dev")
-        out = bytearray(int(used.value))
+        size = 0
+        for i0, m in sizing:
+            rc_ = call(i0, m, None, 0, used)
+            if rc_ not in (N.KMAN_OK, N.KMAN_ECAP):
+                N.check(dev.ctx, rc_, "kman_format_*_dev")
+            size += int(used.value)
+        out = bytearray(size)
         dst0 = ctypes.addressof((ctypes.c_char * max(1, len(out))).from_buffer(out)) if len(out) else 0
     else:
         fd, base = _pwrite_target(sink)
@@ -1169,12 +1219,11 @@ def _format_dev(dev: Device, n: int, row_bytes: int, call, sink=None):
             # zero-copy: the format kernel writes slice i straight into pinned
             # stage b over PCIe (no copy engine); the host drains stage b while
             # slice i + 1 is formatted into the other stage
-            for i, i0 in enumerate(range(0, n, rows)):
+            for i, (i0, m) in enumerate(slices):
                 b = i % NB
                 for f in pending[b]:
                     f.result()
                 pending[b] = []
-                m = min(rows, n - i0)
                 N.check(dev.ctx, call(i0, m, stages[b], cap, used), "kman_format_*_dev")
                 u = int(used.value)
                 if out is None and fd is None:  # a stream: one writer thread keeps the slices in order
@@ -1190,12 +1239,11 @@ def _format_dev(dev: Device, n: int, row_bytes: int, call, sink=None):
                 for f in pb:
                     f.result()
         else:
-            for i, i0 in enumerate(range(0, n, rows)):
+            for i, (i0, m) in enumerate(slices):
                 b = i % NB
                 for f in pending[b]:  # slice i - 2 out of stage b (its D2H finished before)
                     f.result()
                 pending[b] = []
-                m = min(rows, n - i0)
                 N.check(dev.ctx, call(i0, m, c_void_p(dbufs[b].ptr), cap, used), "kman_format_*_dev")
                 u = int(used.value)
                 N.check(dev.ctx, L.kman_copy_d2h_async(dev.ctx, stages[b], c_void_p(dbufs[b].ptr), u, b),
@@ -2167,6 +2215,144 @@ def emit_bed(p: Parsed, span, keep, sink=None):
         kp = keep.ctypes.data_as(c_void_p)
     return _to(sink, _format(N.lib().kman_format_bed, start.ctypes.data_as(c_void_p), end.ctypes.data_as(c_void_p), R,
                              kp, p.names_blob, off.ctypes.data_as(c_void_p)))
+
+
+_CUT_MAX_RECORDS = 1 << 24  # records per slice of cut_records (its work memory: 16 B each, 64 B under trim)
+
+
+def _keep_array(keep, R: int):
+    if keep is None:
+        return None
+    keep = np.ascontiguousarray(keep, dtype=np.uint8)
+    if keep.shape != (R,):
+        raise AssertionError("keep mask of %r for %d records" % (keep.shape, R))
+    return keep
+
+
+def _cut_slices(bound: np.ndarray, limit: int):
+    """(i0, records, text bound) per slice: as many records as fit `limit`
+    bytes of text bound (at most _CUT_MAX_RECORDS), at least one, so a record
+    larger than `limit` gets a slice of its own."""
+    cum = np.cumsum(bound, dtype=np.uint64)
+    R, i0, done, res = len(bound), 0, 0, []
+    while i0 < R:
+        j = int(np.searchsorted(cum, np.uint64(done + limit), side="right"))
+        j = min(max(j, i0 + 1), i0 + _CUT_MAX_RECORDS, R)
+        res.append((i0, j - i0, int(cum[j - 1]) - done))
+        i0, done = j, int(cum[j - 1])
+    return res
+
+
+def cut_records(p: Parsed, keep, sink=None, *, span=None, trim=False):
+    """The text of the records of p with keep != 0 (None: all), in input order
+    (kman_cut_records), from the device text that parse(..., keep_text=True)
+    left in ``p.text``: record r is the input's bytes from rec_hdr[r] to
+    rec_hdr[r + 1] (the last one runs to the text's end), verbatim.  With
+    `trim` (FASTQ records; `span`: solid_spans()'s pair) every record is cut to
+    its columns [START, END): header, sequence[START:END], the ``+`` line and
+    quality[START:END], each followed by ``"\\n"``; a record with END <= START
+    is left out.  Returned (a bytearray), or written to the binary file `sink`,
+    through _format_dev's pinned stages and writer pool, in slices of whole
+    records chosen from rec_hdr (a record's text is at most its bytes + 4); a
+    record larger than a slice gets a slice, and stages, sized for it."""
+    if p.text is None:
+        raise AssertionError("cut_records needs the input text on the device: parse with keep_text=True")
+    dev, L, R, n = p.dev, N.lib(), int(p.n_records), int(p.text_bytes)
+    keep = _keep_array(keep, R)
+    if trim and span is None:
+        raise AssertionError("trim needs the span arrays")
+    if span is not None and not trim:
+        raise AssertionError("span arrays are for trim=True")
+    if R == 0:
+        return None if sink is not None else bytearray()
+    off = np.empty(R + 1, dtype=np.uint64)
+    off[:R] = p.rec_hdr
+    off[R] = n
+    ends = np.minimum(off[1:], np.uint64(n)).astype(np.int64)
+    bound = np.maximum(ends - np.minimum(off[:R], np.uint64(n)).astype(np.int64), 0) + 4
+    if keep is not None:
+        bound[keep == 0] = 0
+    slices = _cut_slices(bound, _FMT_SLICE)
+    flags = N.KMAN_CUT_TRIM if trim else 0
+    need = c_uint64(0)
+    N.check(dev.ctx, L.kman_cut_records_plan(max(m for _, m, _ in slices), flags, byref(need)),
+            "kman_cut_records_plan")
+    bufs = []
+    try:
+        def up(a):
+            b = dev.alloc(a.nbytes)
+            bufs.append(b)
+            dev.upload(b, a)
+            return b.ptr
+
+        d_off = up(off)
+        d_keep = up(keep) if keep is not None else None
+        d_start = d_end = None
+        if trim:
+            start, end = _span_arrays(span, R)
+            d_start, d_end = up(start), up(end)
+        d_work = dev.alloc(need.value)
+        bufs.append(d_work)
+
+        def at(ptr, nbytes):
+            return c_void_p(ptr + nbytes) if ptr is not None else None
+
+        def call(i0, m, d_out, cap, used):
+            return L.kman_cut_records(dev.ctx, c_void_p(p.text.ptr), n, at(d_off, 8 * i0), m, at(d_keep, i0),
+                                      at(d_start, 8 * i0), at(d_end, 8 * i0), flags, c_void_p(d_work.ptr), need.value,
+                                      d_out, cap, byref(used))
+
+        return _format_dev(dev, R, 0, call, sink, slices=slices)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def _cut_host(text: bytes, off, keep, span, trim: bool) -> bytes:
+    """cut_records' bytes by a plain host loop (KMAN_HOST_FORMAT)."""
+    import re
+
+    out = []
+    for r in range(len(off) - 1):
+        if keep is not None and not keep[r]:
+            continue
+        rec = text[int(off[r]):int(off[r + 1])]
+        if not trim:
+            out.append(rec)
+            continue
+        s, e = int(span[0][r]), int(span[1][r])
+        lines = (re.split(rb"\r\n|\n|\r", rec) + [b""] * 4)[:4]
+        body = lines[1].rstrip(b" \t\n\r\v\f\x1c\x1d\x1e\x1f")
+        cols = [c for c in range(len(body)) if body[c] not in b" \r"]
+        e = min(e, len(cols))
+        if s >= e:
+            continue
+        c0, c1 = cols[s], cols[e - 1] + 1
+        out.append(lines[0] + b"\n" + lines[1][c0:c1] + b"\n" + lines[2] + b"\n" + lines[3][c0:c1] + b"\n")
+    return b"".join(out)
+
+
+def emit_reads(p: Parsed, keep, sink, *, span=None, trim=False):
+    """`kmer screen --reads-out`: cut_records of the listed records; under
+    `trim` the listed records without a stretch (END == START) are left out,
+    as emit_bed leaves them out.  KMAN_HOST_FORMAT=1: a host loop over the
+    downloaded text instead of the device kernels."""
+    R = int(p.n_records)
+    keep = _keep_array(keep, R)
+    if trim:
+        if span is None:
+            raise AssertionError("trim needs the span arrays")
+        start, end = _span_arrays(span, R)
+        keep = (np.ones(R, np.uint8) if keep is None else keep.copy())
+        keep[end == start] = 0
+        span = (start, end)
+    if host_format():
+        if p.text is None:
+            raise AssertionError("emit_reads needs the input text on the device: parse with keep_text=True")
+        text = p.dev.download(p.text, p.text_bytes, np.uint8).tobytes()
+        off = list(p.rec_hdr) + [p.text_bytes]
+        return _to(sink, _cut_host(text, off, keep, span, trim))
+    return cut_records(p, keep, sink, span=span, trim=trim)
 
 
 def join_groups(p: Parsed, k: int, rc: bool, mode: str, max_keys: Optional[int] = None, canonical: bool = False):

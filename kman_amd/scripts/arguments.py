@@ -210,6 +210,21 @@ def bed():
                              "in input order, to FILE. Needs --solid")
 
 
+def reads_out():
+    return click.option("--reads-out", "reads_out", type=click.Path(dir_okay=False, writable=True), default=None,
+                        metavar="FILE",
+                        help="Also write the written records themselves, byte for byte as READS has them (fasta or "
+                             "fastq), in input order, to FILE, cut out on the GPU. Always uncompressed: a FILE "
+                             "that ends in .gz is refused")
+
+
+def trim():
+    return click.option("--trim", "trim", is_flag=True, default=False,
+                        help="Cut every read of --reads-out to its solid stretch: sequence and quality columns "
+                             "[START, END), line ends written as \"\\n\"; reads without a stretch are left out. "
+                             "Needs --solid, --reads-out and fastq READS")
+
+
 def index_bits():
     return click.option("--index-bits", "index_bits", type=click.IntRange(1, 24), default=None,
                         help="Key bits of the table's prefix index (at most 2 K). Default: about 8 rows per bucket")

@@ -399,8 +399,14 @@ non-ACGT letters count (and end a stretch, as do bases masked by -q), line
 breaks of a multi-line fasta do not; a record without such a k-mer has 0 and 0.
 --min-solid-len N selects records with END - START >= N; --bed FILE also writes
 "NAME<TAB>START<TAB>END" for the written records that have a stretch, the
-regions that e.g. `seqtk subseq` cuts out; both need --solid.  Launched one
-process per GPU, the command runs on rank 0 alone.
+regions that e.g. `seqtk subseq` cuts out; both need --solid.  --reads-out
+FILE also writes the written records themselves to FILE, byte for byte as READS
+has them, cut out of the input text on the GPU (kman_cut_records); FILE is
+never compressed.  --trim cuts each of them to its solid stretch: the header
+line, the sequence columns [START, END), the "+" line and the same columns of
+the quality line, every line ended by "\n"; reads without a stretch are left
+out as --bed leaves them out; it needs --solid, --reads-out and fastq READS.
+Launched one process per GPU, the command runs on rank 0 alone.
 """)
 @args.reads_path()
 @args.table_input()
@@ -421,18 +427,21 @@ process per GPU, the command runs on rank 0 alone.
 @args.solid()
 @args.min_solid_len()
 @args.bed()
+@args.reads_out()
+@args.trim()
 @args.index_bits()
 def screen(reads_path: str, table_input: str, output_path: str, k: int, canonical: bool = False,
            input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33", min_count: int = 1,
            max_count: Optional[int] = None, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False,
            index_bits: Optional[int] = None, median: bool = False, min_median: Optional[int] = None,
            max_median: Optional[int] = None, solid: Optional[int] = None, min_solid_len: Optional[int] = None,
-           bed_path: Optional[str] = None) -> None:
+           bed_path: Optional[str] = None, reads_out: Optional[str] = None, trim: bool = False) -> None:
     input_file_exists(reads_path)
     input_file_exists(table_input)
     fastq = [_is_fastq(p, input_format) for p in (reads_path, table_input)]
     _check_screen_options(k, min_qual, fastq, min_count, max_count, min_hits, min_frac, index_bits, min_median,
-                          max_median, solid, min_solid_len, bed_path)
+                          max_median, solid, min_solid_len, bed_path, reads_out=reads_out, trim=trim,
+                          output_path=output_path)
     median = median or min_median is not None or max_median is not None
     if launch.distributed() and not launch.solo_rank():
         launch.log_solo("kmer screen")  # (the table and the reads on one GPU: DESIGN §8)
@@ -453,7 +462,11 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
             ranged = engine.filtered_copy(dev, table, min_count, max_count)
             engine.free_result(table)
             table = ranged
-        p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset))
+        if reads_out is None:  # (not one allocation or call differs from a run without the option)
+            p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset))
+        else:
+            p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset),
+                                  keep_text=True)
         try:
             span = None
             if solid is not None:
@@ -474,6 +487,9 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
             if bed_path is not None:
                 with open(bed_path, "wb") as fh:
                     engine.emit_bed(p, span, keep, fh)
+            if reads_out is not None:
+                with open(reads_out, "wb") as fh:
+                    engine.emit_reads(p, keep, fh, span=span if trim else None, trim=trim)
         finally:
             p.free()
     finally:
@@ -484,7 +500,9 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
 def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_count: Optional[int], min_hits: int,
                           min_frac: float, index_bits: Optional[int], min_median: Optional[int] = None,
                           max_median: Optional[int] = None, solid: Optional[int] = None,
-                          min_solid_len: Optional[int] = None, bed_path: Optional[str] = None) -> None:
+                          min_solid_len: Optional[int] = None, bed_path: Optional[str] = None, *,
+                          reads_out: Optional[str] = None, trim: bool = False,
+                          output_path: Optional[str] = None) -> None:
     """What `kmer screen` refuses, before any device work or output."""
     if k <= 1:
         raise AssertionError("k must be >= 1, got %d instead." % k)
@@ -515,6 +533,23 @@ def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_coun
             raise AssertionError("--min-solid-len must be >= 0, got %d" % min_solid_len)
     if bed_path is not None and solid is None:
         raise AssertionError("--bed needs --solid")
+    if trim:
+        if solid is None:
+            raise AssertionError("--trim needs --solid")
+        if reads_out is None:
+            raise AssertionError("--trim needs --reads-out")
+        if not fastq[0]:
+            raise AssertionError("--trim needs fastq READS")
+    if reads_out is not None:
+        if reads_out.endswith(".gz"):
+            raise AssertionError("--reads-out writes plain text: %r ends in .gz" % reads_out)
+        for name, other in (("OUTPUT", output_path), ("--bed", bed_path)):
+            if other is not None and _same_path(reads_out, other):
+                raise AssertionError("--reads-out and %s name the same file, %r" % (name, reads_out))
+
+
+def _same_path(a: str, b: str) -> bool:
+    return os.path.abspath(a) == os.path.abspath(b)
 
 
 if __name__ == "__main__":
