@@ -685,6 +685,66 @@ int kman_screen_records(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases,
                         uint32_t t_count_bytes, uint64_t nt, const uint64_t *d_index, uint32_t index_bits,
                         uint64_t *d_out);
 
+/* ------------------------------------------- reads among several references
+ * Not in the reference: for every record of a parsed input, how many of its
+ * k-mer windows occur in each of up to KMAN_CLASSIFY_MAX_COLORS references.
+ * The COLOURED TABLE is the union of the references' k-mers (d_tkeys strictly
+ * ascending, as every table here) with one u64 mask per row: bit c is set when
+ * reference c holds the key (kman_amd/engine.py color_table builds it from
+ * count tables with kman_or_u64, kman_match_counts and kman_merge_runs).
+ *
+ * kman_classify_records: d_codes, n_bases, k, d_rec_seq, n_records, the table
+ *   (d_tkeys, nt), d_index and index_bits are kman_screen_records' arguments,
+ *   with its record ownership (upper_bound - 1), its empty records, its
+ *   n_bases < k, nt == 0 and n_records == 0 cases and its bounds (a foreign
+ *   index or unsorted keys give wrong counts, never a wild address or an
+ *   endless loop).  d_tmasks: nt u64 masks.  flags: KMAN_CANONICAL and
+ *   KMAN_CLASSIFY_SPECIFIC, anything else KMAN_EINVAL.  n_colors outside
+ *   1..KMAN_CLASSIFY_MAX_COLORS: KMAN_EINVAL.  A refused call writes nothing.
+ *   d_out, 1 + n_colors planes of n_records u32, zeroed by the call itself:
+ *     d_out[r]                        the valid windows that start in record r
+ *     d_out[(1 + c) * n_records + r]  how many of them have their key (the
+ *                                     canonical key under KMAN_CANONICAL) in a
+ *                                     row whose mask has bit c set; under
+ *                                     KMAN_CLASSIFY_SPECIFIC only when the
+ *                                     mask, cut to its bits < n_colors, is
+ *                                     1 << c exactly (no other reference of
+ *                                     the call holds the k-mer)
+ *   Mask bits at or above n_colors are ignored.  Counts are modulo 2^32 (a
+ *   record of 2^32 or more bases: kman_amd/engine.py classify refuses it).
+ *   One block per tile of KMAN_SCREEN_TILE windows and ONE lookup per window
+ *   whatever n_colors is (kman_screen_records' lookup with the masks as the
+ *   counts); the colours are then reduced in chunks of 8 over masks held in
+ *   registers: n_colors <= 8 is one chunk, and a chunk none of whose colours
+ *   occurs in the tile is skipped.  Each (tile, record, plane) adds to d_out
+ *   with at most one 32-bit atomic.  The tile's slice of d_rec_seq is staged
+ *   in LDS when it has at most KMAN_SCREEN_REC_CAP entries and searched in
+ *   global memory otherwise.  Launches are timed under the tag "classify".
+ *   Synchronises.
+ *
+ * kman_classify_pick: d_planes is kman_classify_records' d_out (1 + n_colors
+ *   planes of n_records u32; plane 0 is not read).  d_pick, three planes of
+ *   n_records u32, every word written:
+ *     d_pick[r]                  the lowest-indexed colour with the largest
+ *                                hit count, KMAN_CLASSIFY_NONE when that is 0
+ *     d_pick[n_records + r]      that largest count
+ *     d_pick[2 * n_records + r]  the largest count among the other colours
+ *                                (equal to the largest on a tie; 0 when
+ *                                n_colors == 1)
+ *   n_colors outside 1..KMAN_CLASSIFY_MAX_COLORS or a NULL pointer with
+ *   n_records > 0: KMAN_EINVAL, nothing written.  n_records == 0: nothing is
+ *   done.  One thread per record, the planes read coalesced across records.
+ *   Launches are timed under "classify_pick".  Synchronises. */
+#define KMAN_CLASSIFY_MAX_COLORS 64
+#define KMAN_CLASSIFY_SPECIFIC 16u
+#define KMAN_CLASSIFY_NONE 0xFFFFFFFFu
+int kman_classify_records(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases, uint32_t k, uint32_t flags,
+                          const uint64_t *d_rec_seq, uint64_t n_records, const uint64_t *d_tkeys,
+                          const uint64_t *d_tmasks, uint64_t nt, const uint64_t *d_index, uint32_t index_bits,
+                          uint32_t n_colors, uint32_t *d_out);
+int kman_classify_pick(kman_ctx *ctx, const uint32_t *d_planes, uint64_t n_records, uint32_t n_colors,
+                       uint32_t *d_pick);
+
 /* ------------------------------------------- per-record order statistic
  * Not in the reference: one quantile (the median, by default) of the table
  * counts of a record's k-mer windows.  A sum commutes and an order statistic
@@ -929,6 +989,19 @@ int kman_format_screen_solid(const uint64_t *out3, const uint32_t *median, const
  * input order. */
 int kman_format_bed(const uint64_t *start, const uint64_t *end, uint64_t n_records, const uint8_t *keep,
                     const char *names, const uint64_t *name_off, char *buf, size_t cap, size_t *used, int threads);
+/* `kmer classify` lines, one "%s\t%u\t%s\t%u\t%u\n" (name, windows[r], LABEL,
+ * hits[r], second[r]) per record r with keep[r] != 0 (keep == NULL: every
+ * record), in input order.  LABEL: label assign[r] (labels / label_off as
+ * names / name_off, n_colors of them) when assign[r] >= 0, "?" when it is -2
+ * (ambiguous), "-" for any other negative value (unassigned); an assign[r] >=
+ * n_colors is KMAN_EINVAL.  planes != NULL (n_colors planes of n_records u32,
+ * kman_classify_records' d_out without its first plane) appends one "\t%u"
+ * column per colour, in colour order.  n_colors in
+ * 1..KMAN_CLASSIFY_MAX_COLORS. */
+int kman_format_classify(const uint32_t *windows, const int32_t *assign, const uint32_t *hits, const uint32_t *second,
+                         const uint32_t *planes, uint32_t n_colors, uint64_t n_records, const uint8_t *keep,
+                         const char *labels, const uint64_t *label_off, const char *names, const uint64_t *name_off,
+                         char *buf, size_t cap, size_t *used, int threads);
 
 /* The same writers on the device: the output text is built in
  * HBM (d_out, 16-byte aligned) from device-resident results, so only the text

@@ -54,6 +54,9 @@ KMAN_RUNS_REC_CAP = 512  # rec_seq entries of a tile staged in LDS; more: search
 KMAN_CUT_TRIM = 1  # kman_cut_records: cut every record to its column interval (include/kman.h)
 KMAN_CUT_TILE = 16384  # output bytes per block of kman_cut_records' copy pass
 KMAN_CUT_SEG_CAP = 1024  # segments of a tile staged in LDS; more: searched in global memory
+KMAN_CLASSIFY_MAX_COLORS = 64  # references of one coloured table: a row's mask is one u64 (include/kman.h)
+KMAN_CLASSIFY_SPECIFIC = 16  # kman_classify_records: count a window only for the one reference that holds it
+KMAN_CLASSIFY_NONE = 0xFFFFFFFF  # kman_classify_pick: no colour has a hit
 KMAN_MATCH_RIGHT = 0
 KMAN_MATCH_LEFT = 1
 KMAN_MATCH_MIN = 2
@@ -231,6 +234,15 @@ SIGNATURES = {
     "kman_screen_records": (
         c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32,
                 c_uint64, c_void_p, c_uint32, c_void_p],
+    ),
+    "kman_classify_records": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64,
+                c_void_p, c_uint32, c_uint32, c_void_p],
+    ),
+    "kman_classify_pick": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p]),
+    "kman_format_classify": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_char_p, c_void_p,
+                c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t), c_int],
     ),
     "kman_format_screen": (
         c_int, [c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t), c_int],

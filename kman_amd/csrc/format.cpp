@@ -408,6 +408,59 @@ extern "C" int kman_format_bed(const uint64_t *start, const uint64_t *end, uint6
     return run_sliced(n_records, buf, cap, used, threads, size_of, write_at);
 }
 
+// "%s\t%d\t%s\t%d\t%d\n" % (name, windows, label | "?" | "-", hits, second)
+// per kept record, with one "\t%d" per colour appended when `planes` is given
+// (`kmer classify`, `--hits`; not in the reference)
+extern "C" int kman_format_classify(const uint32_t *windows, const int32_t *assign, const uint32_t *hits,
+                                    const uint32_t *second, const uint32_t *planes, uint32_t n_colors,
+                                    uint64_t n_records, const uint8_t *keep, const char *labels,
+                                    const uint64_t *label_off, const char *names, const uint64_t *name_off, char *buf,
+                                    size_t cap, size_t *used, int threads) {
+    if (!used || n_colors < 1 || n_colors > KMAN_CLASSIFY_MAX_COLORS || !label_off) return KMAN_EINVAL;
+    if (n_records && (!windows || !assign || !hits || !second || !name_off)) return KMAN_EINVAL;
+    for (uint64_t r = 0; r < n_records; r++)
+        if (assign[r] >= 0 && (uint32_t)assign[r] >= n_colors) return KMAN_EINVAL;
+    auto label_len = [&](uint64_t r) -> size_t {
+        return assign[r] >= 0 ? (size_t)(label_off[assign[r] + 1] - label_off[assign[r]]) : 1;
+    };
+    auto size_of = [&](uint64_t r) -> size_t {
+        if (keep && !keep[r]) return 0;
+        size_t s = (name_off[r + 1] - name_off[r]) + 5 + ndigits(windows[r]) + label_len(r) + ndigits(hits[r]) +
+                   ndigits(second[r]);
+        if (planes)
+            for (uint32_t c = 0; c < n_colors; c++) s += 1 + ndigits(planes[(uint64_t)c * n_records + r]);
+        return s;
+    };
+    auto write_at = [&](uint64_t r, char *p) -> char * {
+        if (keep && !keep[r]) return p;
+        const uint64_t L = name_off[r + 1] - name_off[r];
+        if (L) memcpy(p, names + name_off[r], L);
+        p += L;
+        *p++ = '\t';
+        p = put_u64(p, windows[r]);
+        *p++ = '\t';
+        if (assign[r] >= 0) {
+            const size_t n = label_len(r);
+            if (n) memcpy(p, labels + label_off[assign[r]], n);
+            p += n;
+        } else {
+            *p++ = assign[r] == -2 ? '?' : '-';
+        }
+        *p++ = '\t';
+        p = put_u64(p, hits[r]);
+        *p++ = '\t';
+        p = put_u64(p, second[r]);
+        if (planes)
+            for (uint32_t c = 0; c < n_colors; c++) {
+                *p++ = '\t';
+                p = put_u64(p, planes[(uint64_t)c * n_records + r]);
+            }
+        *p++ = '\n';
+        return p;
+    };
+    return run_sliced(n_records, buf, cap, used, threads, size_of, write_at);
+}
+
 // k in 33..64: keys as (hi, lo) word pairs (kman_extract_wide)
 extern "C" int kman_format_count_wide(const uint64_t *hi, const uint64_t *lo, const void *counts, uint32_t count_bytes,
                                       uint64_t n, uint32_t k, char *out, size_t cap, size_t *used, int threads) {

@@ -2355,6 +2355,192 @@ def emit_reads(p: Parsed, keep, sink, *, span=None, trim=False):
     return cut_records(p, keep, sink, span=span, trim=trim)
 
 
+# ------------------------------------------------- reads among references (classify)
+
+MAX_COLORS = N.KMAN_CLASSIFY_MAX_COLORS
+UNASSIGNED, AMBIGUOUS = -1, -2  # classify_assign's values below the colours
+
+
+def color_table(dev: Device, tables) -> CountResult:
+    """The coloured table of 1..64 key-sorted distinct count tables of one k
+    (join_groups(.., "count")): the union of their keys with count_bytes == 8,
+    the "count" of a row being the mask of the tables that hold its key, bit c
+    for tables[c].  The tables are CONSUMED: each one's buffers are freed as
+    soon as it is folded in, so the peak is the union so far plus one table
+    (free_result on them afterwards is harmless).  An empty table is legal:
+    its colour is never hit.
+    Table c's counts become 8-byte words all equal to 1 << c (kman_memset,
+    kman_or_u64) and the table is folded into the running union with
+    set_op(.., "union", "sum"): the bits are disjoint, so the sum is the OR,
+    it never carries (KMAN_MATCH_ANY_SUM saturates only on a carry) and a mask
+    with bit 63 set is inside filter_counts' unsigned range [1, 2^64 - 1]."""
+    tables = list(tables)
+    if not 1 <= len(tables) <= MAX_COLORS:
+        raise AssertionError("a coloured table takes 1 to %d tables, got %d" % (MAX_COLORS, len(tables)))
+    k = tables[0].k
+    if k > MAX_K:
+        raise AssertionError("a coloured table takes k <= %d (one 64-bit key per k-mer), got %d" % (MAX_K, k))
+    for t in tables:
+        if t.k != k:
+            raise AssertionError("the tables hold k-mers of different k: %d and %d" % (k, t.k))
+    acc = None
+    try:
+        for c, t in enumerate(tables):
+            m = dev.alloc(8 * max(t.n, 1))
+            try:
+                if t.n:
+                    dev.memset(m, 0, 8 * t.n)
+                    N.check(dev.ctx, N.lib().kman_or_u64(dev.ctx, c_void_p(m.ptr), t.n, 1 << c), "kman_or_u64")
+            except BaseException:
+                m.free()
+                raise
+            t.counts.free()
+            # the table's keys move to the coloured rows: a new handle owns the allocation, the table's is emptied
+            ukeys = object.__new__(DeviceBuffer)
+            ukeys.dev, ukeys.ptr, ukeys.nbytes = t.ukeys.dev, t.ukeys.ptr, t.ukeys.nbytes
+            t.ukeys.ptr = None
+            col = CountResult(ukeys, m, 8, t.n, k)
+            t.n = 0
+            if acc is None:
+                acc = col
+                continue
+            try:
+                u = set_op(dev, acc, col, "union", "sum")
+            finally:
+                free_result(col)
+            free_result(acc)
+            acc = u
+        res, acc = acc, None
+        return res
+    finally:
+        free_result(acc)
+
+
+def classify(p: Parsed, ctable: CountResult, n_colors: int, canonical: bool = False, specific: bool = False,
+             index: Optional[DeviceBuffer] = None, index_bits: Optional[int] = None, planes: bool = False):
+    """kman_classify_records + kman_classify_pick: for every record of p,
+    (windows, best, hits, second), four u32 arrays of n_records: its valid
+    k-mer windows, the lowest-indexed reference with the most hits
+    (N.KMAN_CLASSIFY_NONE when nothing hit), those hits, and the most hits
+    among the other references.  `ctable`: color_table()'s result for
+    n_colors references, k = ctable.k.  specific: a window counts only for the
+    one reference that holds its k-mer.  canonical, index, index_bits as for
+    screen().  planes: a fifth result, the (n_records, n_colors) u32 hits of
+    every reference; without it only the windows plane and the three picked
+    planes leave the device."""
+    if ctable.k > MAX_K:
+        raise AssertionError("classify takes k <= %d (one 64-bit key per k-mer), got %d" % (MAX_K, ctable.k))
+    if isinstance(n_colors, bool) or not isinstance(n_colors, (int, np.integer)) or not 1 <= n_colors <= MAX_COLORS:
+        raise AssertionError("n_colors must be an integer in [1, %d], got %r" % (MAX_COLORS, n_colors))
+    if ctable.count_bytes != 8:
+        raise AssertionError("classify takes a coloured table (8-byte masks: color_table), got %d-byte counts"
+                             % ctable.count_bytes)
+    dev, k, R, nc = p.dev, ctable.k, int(p.n_records), int(n_colors)
+    bits = default_index_bits(ctable.n, k) if index_bits is None else _check_index_bits(index_bits, k)
+    rec_seq = np.ascontiguousarray(p.rec_seq, dtype=np.uint64)
+    if R:
+        ends = np.concatenate([rec_seq[1:], np.asarray([p.n_bases], dtype=np.uint64)])
+        if int((ends - np.minimum(rec_seq, ends)).max()) >= 1 << 32:
+            raise AssertionError("classify counts in 32 bits: a record of 2^32 or more bases is refused")
+    if R == 0:
+        z = np.zeros(0, np.uint32)
+        return (z, z.copy(), z.copy(), z.copy()) + ((np.zeros((0, nc), np.uint32),) if planes else ())
+    flags = (N.KMAN_CANONICAL if canonical else 0) | (N.KMAN_CLASSIFY_SPECIFIC if specific else 0)
+    own = d_rec = d_out = d_pick = None
+    try:
+        if index is None:
+            index = own = table_index(dev, ctable, bits)
+        d_rec = dev.alloc(8 * R)
+        dev.upload(d_rec, rec_seq)
+        d_out = dev.alloc(4 * (1 + nc) * R)
+        d_pick = dev.alloc(12 * R)
+        N.check(dev.ctx, N.lib().kman_classify_records(
+            dev.ctx, c_void_p(p.codes.ptr), p.n_bases, k, flags, c_void_p(d_rec.ptr), R, c_void_p(ctable.ukeys.ptr),
+            c_void_p(ctable.counts.ptr), ctable.n, c_void_p(index.ptr), bits, nc, c_void_p(d_out.ptr)),
+            "kman_classify_records")
+        N.check(dev.ctx, N.lib().kman_classify_pick(dev.ctx, c_void_p(d_out.ptr), R, nc, c_void_p(d_pick.ptr)),
+                "kman_classify_pick")
+        windows = dev.download(d_out, R, np.uint32)
+        pick = dev.download(d_pick, 3 * R, np.uint32).reshape(3, R)
+        res = (windows, pick[0].copy(), pick[1].copy(), pick[2].copy())
+        if planes:
+            res += (np.ascontiguousarray(dev.download(d_out, nc * R, np.uint32, 4 * R).reshape(nc, R).T),)
+        return res
+    finally:
+        for b in (own, d_rec, d_out, d_pick):
+            if b is not None:
+                b.free()
+
+
+def classify_assign(windows, best, hits, second, min_hits: int = 1, min_frac: float = 0.0,
+                    min_margin: int = 1) -> np.ndarray:
+    """The reference each record of classify()'s arrays is assigned to, an
+    int32 array: UNASSIGNED (-1) when hits < max(min_hits, 1) or hits <
+    min_frac * windows (float64), else AMBIGUOUS (-2) when hits - second <
+    min_margin, else `best`.  min_margin >= 1: a tie is never decided by the
+    order of the references."""
+    for name, v in (("min_hits", min_hits), ("min_margin", min_margin)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise AssertionError("%s must be an integer, got %r" % (name, v))
+    if min_hits < 0:
+        raise AssertionError("min_hits must be >= 0, got %d" % min_hits)
+    if min_margin < 1:
+        raise AssertionError("min_margin must be >= 1, got %d" % min_margin)
+    if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or \
+            not 0.0 <= min_frac <= 1.0:  # (a NaN is refused too)
+        raise AssertionError("min_frac must be in [0, 1], got %r" % (min_frac,))
+    w, b, h, s = (np.asarray(a, dtype=np.uint32).reshape(-1) for a in (windows, best, hits, second))
+    if not (w.shape == b.shape == h.shape == s.shape):
+        raise AssertionError("classify_assign: arrays of %r, %r, %r and %r" % (w.shape, b.shape, h.shape, s.shape))
+    hf, h64 = h.astype(np.float64), h.astype(np.int64)
+    un = (h64 < max(int(min_hits), 1)) | (hf < float(min_frac) * w.astype(np.float64)) | \
+        (b == np.uint32(N.KMAN_CLASSIFY_NONE))
+    amb = (h64 - s.astype(np.int64)) < int(min_margin)
+    out = np.where(un, UNASSIGNED, np.where(amb, AMBIGUOUS, b.astype(np.int64)))
+    return out.astype(np.int32)
+
+
+def _label_blob(labels):
+    labels = [x if isinstance(x, bytes) else str(x).encode("utf-8", errors="surrogateescape") for x in labels]
+    if not 1 <= len(labels) <= MAX_COLORS:
+        raise AssertionError("1 to %d labels, got %d" % (MAX_COLORS, len(labels)))
+    off = np.zeros(len(labels) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in labels])
+    return b"".join(labels), off
+
+
+def emit_classify(p: Parsed, labels, windows, assign, hits, second, sink=None, *, planes=None, keep=None):
+    """The `kmer classify` text: one "name<TAB>windows<TAB>LABEL<TAB>hits<TAB>
+    second" line per record with keep != 0 (None: all), in input order
+    (kman_format_classify); LABEL is labels[assign], "?" for AMBIGUOUS, "-" for
+    UNASSIGNED.  `planes` (classify(.., planes=True)'s (n_records, n_colors)
+    array) appends one column per reference.  Returned, or written to the
+    binary file `sink`."""
+    R = int(p.n_records)
+    blob, loff = _label_blob(labels)
+    nc = len(loff) - 1
+    w, h, s = (np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (windows, hits, second))
+    a = np.ascontiguousarray(assign, dtype=np.int32).reshape(-1)
+    for x in (w, h, s, a):
+        if x.shape != (R,):
+            raise AssertionError("array of %r for %d records" % (x.shape, R))
+    if R and int(a.max()) >= nc:
+        raise AssertionError("assignment %d with %d labels" % (int(a.max()), nc))
+    pp = None
+    if planes is not None:
+        planes = np.asarray(planes, dtype=np.uint32)
+        if planes.shape != (R, nc):
+            raise AssertionError("hit planes of %r for %d records and %d labels" % (planes.shape, R, nc))
+        planes = np.ascontiguousarray(planes.T)
+        pp = planes.ctypes.data_as(c_void_p)
+    keep = _keep_array(keep, R)
+    kp = keep.ctypes.data_as(c_void_p) if keep is not None else None
+    off = np.ascontiguousarray(p.name_off, dtype=np.uint64)
+    return _to(sink, _format(N.lib().kman_format_classify, w.ctypes.data_as(c_void_p), a.ctypes.data_as(c_void_p),
+                             h.ctypes.data_as(c_void_p), s.ctypes.data_as(c_void_p), pp, nc, R, kp, blob,
+                             loff.ctypes.data_as(c_void_p), p.names_blob, off.ctypes.data_as(c_void_p)))
+
+
 def join_groups(p: Parsed, k: int, rc: bool, mode: str, max_keys: Optional[int] = None, canonical: bool = False):
     """The count / uniq result of the whole stream of p on the device, by the
     fastest path that takes it: the region path (kman_groups); the multi-batch

@@ -230,5 +230,71 @@ def index_bits():
                         help="Key bits of the table's prefix index (at most 2 K). Default: about 8 rows per bucket")
 
 
+def refs():
+    return click.option("--ref", "refs", type=click.Path(exists=True, file_okay=True, dir_okay=False, readable=True),
+                        multiple=True, metavar="FILE",
+                        help="A reference, fasta or fastq, plain or gzipped; 1 to 64 of them. Its label is the "
+                             "file's name without a trailing .gz and then one extension")
+
+
+def classify_canonical():
+    return click.option("--canonical", "canonical", is_flag=True,
+                        help="Canonical k-mers, min(k-mer, reverse complement), in every reference and in the reads")
+
+
+def ref_min_count():
+    return click.option("--min-count", "-L", "min_count", type=click.IntRange(min=1), default=1,
+                        help="Look up only k-mers seen at least this often in their own reference. Default: 1 (all)")
+
+
+def ref_max_count():
+    return click.option("--max-count", "-U", "max_count", type=click.IntRange(min=1), default=None,
+                        help="Look up only k-mers seen at most this often in their own reference. Default: no limit")
+
+
+def specific():
+    return click.option("--specific", "specific", is_flag=True,
+                        help="Count a k-mer only for the one reference that holds it: k-mers shared by two or more "
+                             "references vote for none")
+
+
+def classify_min_hits():
+    return click.option("--min-hits", "min_hits", type=click.INT, default=1,
+                        help="Assign a record only when its best reference has at least this many k-mers found "
+                             "(never with 0). Default: 1")
+
+
+def classify_min_frac():
+    return click.option("--min-frac", "min_frac", type=click.FLOAT, default=0.0,
+                        help="Assign a record only when its best reference has at least this fraction (0..1) of the "
+                             "record's k-mers. Default: 0.0")
+
+
+def min_margin():
+    return click.option("--min-margin", "min_margin", type=click.INT, default=1,
+                        help="A record whose best reference leads the runner-up by fewer k-mers than this is "
+                             "ambiguous ('?'); at least 1, so a tie is always ambiguous. Default: 1")
+
+
+def hits():
+    return click.option("--hits", "hits", is_flag=True,
+                        help="Append one column per reference, in --ref order: the record's k-mers found there")
+
+
+def summary():
+    return click.option("--summary", "summary_path", type=click.Path(dir_okay=False, writable=True), default=None,
+                        metavar="FILE",
+                        help="Also write LABEL<TAB>TABLE_KMERS<TAB>READS per reference, then the '?' and '-' lines, "
+                             "to FILE")
+
+
+def reads_out_prefix():
+    return click.option("--reads-out-prefix", "reads_out_prefix", type=click.Path(dir_okay=False), default=None,
+                        metavar="PREFIX",
+                        help="Also write the records themselves, byte for byte as READS has them, to PREFIX.LABEL.fq "
+                             "(.fa for fasta READS) per reference, PREFIX.ambiguous.* and PREFIX.unassigned.*, cut "
+                             "out on the GPU. Always uncompressed; empty files are still created")
+
+
 def re_sort():
     return click.option("--re-sort", "-R", is_flag=True, help="Force batch re-sorting, when loaded with -B.")

@@ -2,7 +2,7 @@
 
 Same arguments, flags, defaults, outputs and errors as the reference CLI; the
 work runs on the GPU through kman_amd (FastaBatcher.do + KJoiner.join).
-``hist``, ``sets`` and ``screen`` are this engine's own commands.
+``hist``, ``sets``, ``screen`` and ``classify`` are this engine's own commands.
 """
 
 from __future__ import annotations
@@ -550,6 +550,194 @@ def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_coun
 
 def _same_path(a: str, b: str) -> bool:
     return os.path.abspath(a) == os.path.abspath(b)
+
+
+@main.command(name="classify", context_settings=CONTEXT_SETTINGS, help="""
+Assign reads among references: for every record of READS, which of the --ref
+files holds most of its k-mers, written to OUTPUT as one
+"NAME<TAB>K-MERS<TAB>LABEL<TAB>HITS<TAB>SECOND" line per record in input
+order (HITS: the record's k-mers found in the best reference, SECOND: in the
+best of the others).
+
+Not part of the reference kman CLI.  Every --ref is counted on the GPU and the
+tables are united into one coloured table there: each k-mer of any reference
+with the set of references that hold it.  The reads' k-mers are looked up in
+it once, whatever the number of references (kman_classify_records,
+kman_classify_pick); nothing goes through a text file.  READS and every
+--ref: fasta or fastq files, plain or gzipped, each detected on its own.
+K <= 32; 1 to 64 --ref.  LABEL is the reference's label (its file name
+without a trailing .gz and then one extension), "?" for an ambiguous record
+(the best reference leads by fewer than --min-margin k-mers) and "-" for an
+unassigned one (fewer than --min-hits k-mers, never with 0, or less than
+--min-frac of the record's k-mers).  -L / -U select the k-mers of each
+reference, by their count in that reference.  --specific counts a k-mer only
+when exactly one reference holds it, so k-mers shared between references
+(human and mouse, host and vector) vote for none.  --hits appends one column
+per reference.  --summary FILE writes "LABEL<TAB>TABLE_KMERS<TAB>READS" per
+reference (its k-mers after -L / -U, the records assigned to it), then
+"?<TAB>0<TAB>N" and "-<TAB>0<TAB>N".  --reads-out-prefix P writes the
+records themselves to P.LABEL.fq (.fa for fasta READS) per reference,
+P.ambiguous.* and P.unassigned.*, byte for byte as READS has them, cut out on
+the GPU (kman_cut_records) and never compressed.
+Launched one process per GPU, the command runs on rank 0 alone.
+""")
+@args.reads_path()
+@args.output_path(file_okay=True)
+@args.k()
+@args.refs()
+@args.classify_canonical()
+@args.input_format()
+@args.min_qual()
+@args.phred_offset()
+@args.ref_min_count()
+@args.ref_max_count()
+@args.specific()
+@args.classify_min_hits()
+@args.classify_min_frac()
+@args.min_margin()
+@args.hits()
+@args.summary()
+@args.reads_out_prefix()
+@args.index_bits()
+def classify(reads_path: str, output_path: str, k: int, refs=(), canonical: bool = False, input_format: str = "auto",
+             min_qual: int = 0, phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None,
+             specific: bool = False, min_hits: int = 1, min_frac: float = 0.0, min_margin: int = 1,
+             hits: bool = False, summary_path: Optional[str] = None, reads_out_prefix: Optional[str] = None,
+             index_bits: Optional[int] = None) -> None:
+    input_file_exists(reads_path)
+    refs = list(refs)
+    for path in refs:
+        input_file_exists(path)
+    fastq = [_is_fastq(p, input_format) for p in [reads_path] + refs]
+    labels = [ref_label(path) for path in refs]
+    ext = "fq" if fastq[0] else "fa"
+    outs = _classify_outputs(reads_out_prefix, labels, ext)
+    _check_classify_options(k, labels, min_qual, fastq, min_count, max_count, min_hits, min_frac, min_margin,
+                            index_bits, output_path, summary_path, outs)
+    if launch.distributed() and not launch.solo_rank():
+        launch.log_solo("kmer classify")  # (the coloured table and the reads on one GPU: DESIGN §8)
+        return
+    dev = engine.default_device()
+    nc = len(refs)
+    tables, ctable, table_kmers = [], None, []
+    try:
+        for path, fq in zip(refs, fastq[1:]):
+            # (a reference's parse buffers are freed before the next one is read)
+            p = engine.parse_file(dev, path, input_format, min_qual if fq else 0, int(phred_offset))
+            try:
+                engine.check_empty_names(p, k)
+                t = engine.join_groups(p, k, False, "count", canonical=canonical)
+            finally:
+                p.free()
+            if t is None:
+                t = engine.empty_count(dev, k)  # (no k-mers: a colour that is never hit)
+            elif min_count > 1 or max_count is not None:
+                ranged = engine.filtered_copy(dev, t, min_count, max_count)
+                engine.free_result(t)
+                t = ranged
+            tables.append(t)
+            table_kmers.append(int(t.n))
+        ctable = engine.color_table(dev, tables)  # (frees each table as it is folded in)
+        index = engine.table_index(dev, ctable, index_bits)
+        try:
+            p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset),
+                                  keep_text=reads_out_prefix is not None)
+            try:
+                res = engine.classify(p, ctable, nc, canonical, specific, index=index, index_bits=index_bits,
+                                      planes=hits)
+                windows, best, nhits, second = res[:4]
+                assign = engine.classify_assign(windows, best, nhits, second, min_hits, min_frac, min_margin)
+                with open(output_path, "wb") as fh:
+                    engine.emit_classify(p, labels, windows, assign, nhits, second, fh,
+                                         planes=res[4] if hits else None)
+                if summary_path is not None:
+                    with open(summary_path, "wb") as fh:
+                        fh.write(classify_summary(labels, table_kmers, assign))
+                for value, path in outs:
+                    with open(path, "wb") as fh:
+                        engine.emit_reads(p, (assign == value).astype("uint8"), fh)
+            finally:
+                p.free()
+        finally:
+            index.free()
+    finally:
+        for t in tables:
+            engine.free_result(t)
+        engine.free_result(ctable)
+    logging.info("That's all!")
+
+
+RESERVED_LABELS = ("-", "?", "ambiguous", "unassigned")
+
+
+def ref_label(path: str) -> str:
+    """A reference's label: the file's basename minus a trailing .gz and then
+    one extension (a.fa, a.fa.gz -> a; b.fastq.gz -> b; noext -> noext)."""
+    name = os.path.basename(path)
+    if name.endswith(".gz"):
+        name = name[:-3]
+    stem, dot, _ = name.rpartition(".")
+    return stem if dot and stem else name
+
+
+def classify_summary(labels, table_kmers, assign) -> bytes:
+    """`kmer classify --summary`: LABEL<TAB>TABLE_KMERS<TAB>READS per
+    reference, then the ambiguous and the unassigned records."""
+    assign = [int(a) for a in assign]
+    out = ["%s\t%d\t%d\n" % (lab, n, sum(1 for a in assign if a == c))
+           for c, (lab, n) in enumerate(zip(labels, table_kmers))]
+    out.append("?\t0\t%d\n" % sum(1 for a in assign if a == engine.AMBIGUOUS))
+    out.append("-\t0\t%d\n" % sum(1 for a in assign if a == engine.UNASSIGNED))
+    return "".join(out).encode("utf-8", errors="surrogateescape")
+
+
+def _classify_outputs(prefix: Optional[str], labels, ext: str):
+    """(assignment value, path) of every --reads-out-prefix file."""
+    if prefix is None:
+        return []
+    outs = [(c, "%s.%s.%s" % (prefix, lab, ext)) for c, lab in enumerate(labels)]
+    return outs + [(engine.AMBIGUOUS, "%s.ambiguous.%s" % (prefix, ext)),
+                   (engine.UNASSIGNED, "%s.unassigned.%s" % (prefix, ext))]
+
+
+def _check_classify_options(k: int, labels, min_qual: int, fastq, min_count: int, max_count: Optional[int],
+                            min_hits: int, min_frac: float, min_margin: int, index_bits: Optional[int],
+                            output_path: str, summary_path: Optional[str], outs) -> None:
+    """What `kmer classify` refuses, before any device work or output."""
+    if k <= 1:
+        raise AssertionError("k must be >= 1, got %d instead." % k)
+    if k > engine.MAX_K:
+        raise AssertionError("kmer classify takes K <= %d (one 64-bit key per k-mer), got %d: word keys are a stated "
+                             "limit of this command" % (engine.MAX_K, k))
+    if not 1 <= len(labels) <= engine.MAX_COLORS:
+        raise AssertionError("kmer classify takes 1 to %d --ref, got %d" % (engine.MAX_COLORS, len(labels)))
+    seen = set()
+    for lab in labels:
+        if lab in RESERVED_LABELS:
+            raise AssertionError("--ref label %r is reserved (%s): rename the file" % (lab, ", ".join(RESERVED_LABELS)))
+        if "\t" in lab:
+            raise AssertionError("--ref label %r holds a tab" % lab)
+        if lab in seen:
+            raise AssertionError("two --ref have the label %r: labels must differ" % lab)
+        seen.add(lab)
+    if min_qual > 0 and not any(fastq):
+        raise AssertionError("--min-qual needs fastq input: neither READS nor any --ref is fastq")
+    if max_count is not None and min_count > max_count:
+        raise AssertionError("--min-count %d is greater than --max-count %d" % (min_count, max_count))
+    if not 0.0 <= min_frac <= 1.0:  # (a NaN is refused too)
+        raise AssertionError("--min-frac must be in [0, 1], got %r" % min_frac)
+    if min_hits < 0:
+        raise AssertionError("--min-hits must be >= 0, got %d" % min_hits)
+    if min_margin < 1:
+        raise AssertionError("--min-margin must be >= 1, got %d" % min_margin)
+    if index_bits is not None and index_bits > 2 * k:
+        raise AssertionError("--index-bits %d is more than the 2 K = %d bits of a k-mer" % (index_bits, 2 * k))
+    named = [("OUTPUT", output_path)] + ([("--summary", summary_path)] if summary_path is not None else []) + \
+        [("--reads-out-prefix", path) for _, path in outs]
+    for i, (na, pa) in enumerate(named):
+        for nb, pb in named[:i]:
+            if _same_path(pa, pb):
+                raise AssertionError("%s and %s name the same file, %r" % (nb, na, pa))
 
 
 if __name__ == "__main__":
