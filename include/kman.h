@@ -916,6 +916,86 @@ int kman_cut_records(kman_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, con
                      uint64_t n_records, const uint8_t *d_keep, const uint64_t *d_start, const uint64_t *d_end,
                      uint32_t flags, void *d_work, uint64_t work_bytes, char *d_out, size_t cap, size_t *used);
 
+/* ------------------------------------------- isolated substitution errors
+ * Not in the reference: the base that one substitution error changed, put back
+ * from the table (`kmer screen --solid C --correct`).  Over
+ * kman_window_counts' words on these codes, this table, k and flags, window
+ * start b is WEAK when d_wc[b] != KMAN_WC_NONE and d_wc[b] < min_count, SOLID
+ * when d_wc[b] != KMAN_WC_NONE and d_wc[b] >= min_count.  A WEAK RUN [a, b) of
+ * record r (bases [s, e), kman_record_runs' ownership) is a maximal interval
+ * of weak window starts inside [s, e).  With
+ *     L = a > s and a - 1 is solid          openL = a == s
+ *     R = b + k <= e and b is solid         openR = b + k == e + 1
+ * the run names a SITE p in exactly these cases:
+ *     L and R,     b - a == k    p = b - 1
+ *     L and openR, b - a <= k    p = a + k - 1
+ *     openL and R, b - a <= k    p = b - 1
+ * (a KMAN_WC_NONE neighbour, both sides open, L and R with another length: no
+ * site).  The windows of r that cover p are then exactly the run's.  With o
+ * the base at p, ok(x) for x != o: every window of the run, read with x at p,
+ * has a count >= min_count in the table (its canonical key under
+ * KMAN_CANONICAL).  The site is corrected to x when exactly one x is ok.
+ * Sites are judged on the codes and words as given; two sites of a record
+ * never share a window.
+ *
+ * kman_correct_sites: d_codes, n_bases, k (2..32), flags (0 or
+ *   KMAN_CANONICAL), the table, d_index and index_bits as for
+ *   kman_window_counts; d_wc its words on them (16-byte aligned); d_rec_seq,
+ *   n_records and min_count (1..0xFFFFFFFE) as for kman_record_runs.  Checked
+ *   as those two check them: KMAN_EINVAL, and a refused call writes nothing.
+ *   d_fix, n_bases bytes, every one written by the call (it fills the plane
+ *   itself): KMAN_FIX_NONE, or the new 2-bit base of a corrected site.
+ *   *n_fixed (may be NULL): the corrected bases.  Neither d_codes nor d_wc is
+ *   modified.  n_bases < k or n_records == 0: d_fix is KMAN_FIX_NONE
+ *   throughout, *n_fixed = 0, nothing else is launched.  n_bases == 0: nothing
+ *   is done.
+ *   One block of 256 threads per tile of KMAN_CORRECT_TILE bases; the tile's
+ *   words and a halo of 36 go to LDS; the tile's slice of d_rec_seq is staged
+ *   when it has at most KMAN_CORRECT_REC_CAP entries and searched in global
+ *   memory otherwise.  The lane of a run's first base reads at most k more
+ *   words (nothing is carried across tiles); a wave then evaluates its lanes'
+ *   sites one at a time: 64 codes, at most 3 k lookups (kman_screen_records'
+ *   device function and bounds), three votes, one byte stored.  Every byte of
+ *   d_fix has one writer after the fill; the count is one atomic add per wave:
+ *   the same bytes on every call.  A d_wc, index or d_rec_seq that does not
+ *   belong to these codes gives wrong corrections, never a wild address or an
+ *   unbounded loop.  Launches are timed under "correct_sites".  Synchronises.
+ *
+ * kman_apply_fixes: d_fix as kman_correct_sites writes it (16-byte aligned;
+ *   a byte other than KMAN_FIX_NONE is taken modulo 4).
+ *   Codes: d_codes[b] = d_fix[b] | (d_codes[b] & 8) where d_fix[b] !=
+ *   KMAN_FIX_NONE.
+ *   Counts: d_nfix[r] (n_records u32, every word written) = the bytes of d_fix
+ *   that are not KMAN_FIX_NONE among the bases of record r (kman_record_runs'
+ *   ownership).
+ *   Text: d_text NULL, or n_bytes of four-line FASTQ text (16-byte aligned)
+ *   with d_rec_off, kman_cut_records' n_records + 1 offsets (the parser's
+ *   d_rec_hdr followed by n_bytes).  The kept characters of record r are the
+ *   bytes of its second line (kman_cut_records' line rule) that are not ' ',
+ *   in order: the i-th is the character of base d_rec_seq[r] + i (blanks
+ *   inside a sequence line shift code indices), and bytes that the parser's
+ *   right strip removed come after the last base.  The text byte of a fixed
+ *   base becomes "ACGT"[x], "acgt"[x] when the byte it replaces is a lower-case
+ *   letter.  The quality line and every other byte are untouched.
+ *   A NULL pointer with non-zero sizes, d_text without d_rec_off, a misaligned
+ *   d_fix or d_text, more than 2^31 records: KMAN_EINVAL, nothing written.
+ *   One thread per 16 bases for the codes; one wave per record for the count
+ *   and the text (a record of L bytes: about L / 1024 steps of that wave,
+ *   kman_cut_records' limit for very long reads; a record without a fix is
+ *   not searched in the text).  Offsets are clamped to n_bytes and n_bases, a
+ *   descending pair is an empty record.  Launches are timed under
+ *   "apply_fixes".  Synchronises. */
+#define KMAN_FIX_NONE 0xFFu
+#define KMAN_CORRECT_TILE 4096
+#define KMAN_CORRECT_REC_CAP 512
+int kman_correct_sites(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases, uint32_t k, uint32_t flags,
+                       const uint32_t *d_wc, const uint64_t *d_rec_seq, uint64_t n_records, const uint64_t *d_tkeys,
+                       const void *d_tcounts, uint32_t t_count_bytes, uint64_t nt, const uint64_t *d_index,
+                       uint32_t index_bits, uint32_t min_count, uint8_t *d_fix, uint64_t *n_fixed);
+int kman_apply_fixes(kman_ctx *ctx, uint8_t *d_codes, uint64_t n_bases, const uint8_t *d_fix,
+                     const uint64_t *d_rec_seq, uint64_t n_records, uint8_t *d_text, uint64_t n_bytes,
+                     const uint64_t *d_rec_off, uint32_t *d_nfix);
+
 /* kman_rebase_pos: uniq pos tagged with their source shard (bits 56-63) ->
  *   global pos: (pos & (2^56 - 1)) + (offsets[source] << 1), offsets = the
  *   global base index of each shard's first base (host array, nsrc <= 256).
@@ -984,6 +1064,14 @@ int kman_format_screen_median(const uint64_t *out3, const uint32_t *median, uint
 int kman_format_screen_solid(const uint64_t *out3, const uint32_t *median, const uint64_t *start, const uint64_t *end,
                              uint64_t n_records, const uint8_t *keep, const char *names, const uint64_t *name_off,
                              char *buf, size_t cap, size_t *used, int threads);
+/* kman_format_screen_solid's lines with the record's corrected bases as one
+ * last column (`kmer screen --solid C --correct`):
+ * "%s\t%llu\t%llu\t%llu[\t%u]\t%llu\t%llu\t%u\n" (.., start[r], end[r],
+ * fixes[r]: kman_apply_fixes' word of the record). */
+int kman_format_screen_correct(const uint64_t *out3, const uint32_t *median, const uint64_t *start,
+                               const uint64_t *end, const uint32_t *fixes, uint64_t n_records, const uint8_t *keep,
+                               const char *names, const uint64_t *name_off, char *buf, size_t cap, size_t *used,
+                               int threads);
 /* BED lines "%s\t%llu\t%llu\n" (name, start[r], end[r]) for every record r
  * with keep[r] != 0 (keep == NULL: every record) and end[r] > start[r], in
  * input order. */

@@ -54,6 +54,9 @@ KMAN_RUNS_REC_CAP = 512  # rec_seq entries of a tile staged in LDS; more: search
 KMAN_CUT_TRIM = 1  # kman_cut_records: cut every record to its column interval (include/kman.h)
 KMAN_CUT_TILE = 16384  # output bytes per block of kman_cut_records' copy pass
 KMAN_CUT_SEG_CAP = 1024  # segments of a tile staged in LDS; more: searched in global memory
+KMAN_FIX_NONE = 0xFF  # kman_correct_sites: no correction at this base (include/kman.h)
+KMAN_CORRECT_TILE = 4096  # bases per tile of kman_correct_sites
+KMAN_CORRECT_REC_CAP = 512  # rec_seq entries of a tile staged in LDS; more: searched in global memory
 KMAN_CLASSIFY_MAX_COLORS = 64  # references of one coloured table: a row's mask is one u64 (include/kman.h)
 KMAN_CLASSIFY_SPECIFIC = 16  # kman_classify_records: count a window only for the one reference that holds it
 KMAN_CLASSIFY_NONE = 0xFFFFFFFF  # kman_classify_pick: no colour has a hit
@@ -270,6 +273,17 @@ SIGNATURES = {
     "kman_format_bed": (
         c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t),
                 c_int],
+    ),
+    "kman_correct_sites": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
+                c_uint32, c_uint64, c_void_p, c_uint32, c_uint32, c_void_p, POINTER(c_uint64)],
+    ),
+    "kman_apply_fixes": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p],
+    ),
+    "kman_format_screen_correct": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p,
+                c_size_t, POINTER(c_size_t), c_int],
     ),
     "kman_cut_records_plan": (c_int, [c_uint64, c_uint32, POINTER(c_uint64)]),
     "kman_cut_records": (

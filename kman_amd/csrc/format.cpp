@@ -382,6 +382,46 @@ extern "C" int kman_format_screen_solid(const uint64_t *out3, const uint32_t *me
     return run_sliced(n_records, buf, cap, used, threads, size_of, write_at);
 }
 
+// the same lines with the record's corrected bases as one last column
+// (`kmer screen --solid C --correct`)
+extern "C" int kman_format_screen_correct(const uint64_t *out3, const uint32_t *median, const uint64_t *start,
+                                          const uint64_t *end, const uint32_t *fixes, uint64_t n_records,
+                                          const uint8_t *keep, const char *names, const uint64_t *name_off, char *buf,
+                                          size_t cap, size_t *used, int threads) {
+    if (!used || (n_records && (!out3 || !start || !end || !fixes || !name_off))) return KMAN_EINVAL;
+    const uint64_t *w = out3, *h = out3 + n_records, *s = out3 + 2 * n_records;
+    auto size_of = [&](uint64_t r) -> size_t {
+        if (keep && !keep[r]) return 0;
+        return (name_off[r + 1] - name_off[r]) + 7 + ndigits(w[r]) + ndigits(h[r]) + ndigits(s[r]) +
+               (median ? 1 + ndigits(median[r]) : 0) + ndigits(start[r]) + ndigits(end[r]) + ndigits(fixes[r]);
+    };
+    auto write_at = [&](uint64_t r, char *p) -> char * {
+        if (keep && !keep[r]) return p;
+        const uint64_t L = name_off[r + 1] - name_off[r];
+        if (L) memcpy(p, names + name_off[r], L);
+        p += L;
+        *p++ = '\t';
+        p = put_u64(p, w[r]);
+        *p++ = '\t';
+        p = put_u64(p, h[r]);
+        *p++ = '\t';
+        p = put_u64(p, s[r]);
+        if (median) {
+            *p++ = '\t';
+            p = put_u64(p, median[r]);
+        }
+        *p++ = '\t';
+        p = put_u64(p, start[r]);
+        *p++ = '\t';
+        p = put_u64(p, end[r]);
+        *p++ = '\t';
+        p = put_u64(p, fixes[r]);
+        *p++ = '\n';
+        return p;
+    };
+    return run_sliced(n_records, buf, cap, used, threads, size_of, write_at);
+}
+
 // "%s\t%d\t%d\n" % (name, start, end) per kept record with end > start: the
 // BED of the solid spans (`kmer screen --solid C --bed FILE`)
 extern "C" int kman_format_bed(const uint64_t *start, const uint64_t *end, uint64_t n_records, const uint8_t *keep,

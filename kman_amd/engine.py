@@ -2125,6 +2125,65 @@ def screen_solid(p: Parsed, table: CountResult, canonical: bool, min_count: int,
                 b.free()
 
 
+def correct(p: Parsed, table: CountResult, canonical: bool, min_count: int, *, index: Optional[DeviceBuffer] = None,
+            index_bits: Optional[int] = None, d_wc: Optional[DeviceBuffer] = None) -> np.ndarray:
+    """Isolated substitution errors of p's records put right against `table`
+    (kman_correct_sites, kman_apply_fixes; the rule: include/kman.h): a run of
+    at most k window counts below min_count with a count >= min_count next to
+    it names one base, and the base is replaced when exactly one other base
+    makes every window over it reach min_count.  ``p.codes`` is patched in
+    place, and ``p.text`` (four-line FASTQ) when the parse kept it; quality
+    values never change.  Returns the fixes per record, u32.  `d_wc`:
+    window_counts() of p as it is, kept by the caller (not modified; stale
+    afterwards where a base changed); None: computed and freed here.  One
+    pass: the corrected records are not examined again.  index, index_bits as
+    for screen()."""
+    if table.k > MAX_K:
+        raise AssertionError("correct takes k <= %d (one 64-bit key per k-mer), got %d" % (MAX_K, table.k))
+    min_count = _check_min_count(min_count)
+    dev, k, R, n = p.dev, table.k, int(p.n_records), int(p.n_bases)
+    bits = default_index_bits(table.n, k) if index_bits is None else _check_index_bits(index_bits, k)
+    if R == 0 or n == 0:
+        return np.zeros(R, np.uint32)
+    bufs = []
+    try:
+        if index is None:
+            index = table_index(dev, table, bits)
+            bufs.append(index)
+        if d_wc is None:
+            d_wc = window_counts(p, table, canonical, index=index, index_bits=bits)
+            bufs.append(d_wc)
+        d_rec = dev.alloc(8 * R)
+        bufs.append(d_rec)
+        dev.upload(d_rec, np.ascontiguousarray(p.rec_seq, dtype=np.uint64))
+        d_fix = dev.alloc(max(16, n))
+        bufs.append(d_fix)
+        n_fixed = c_uint64(0)
+        N.check(dev.ctx, N.lib().kman_correct_sites(
+            dev.ctx, c_void_p(p.codes.ptr), n, k, N.KMAN_CANONICAL if canonical else 0, c_void_p(d_wc.ptr),
+            c_void_p(d_rec.ptr), R, c_void_p(table.ukeys.ptr), c_void_p(table.counts.ptr), table.count_bytes, table.n,
+            c_void_p(index.ptr), bits, min_count, c_void_p(d_fix.ptr), byref(n_fixed)), "kman_correct_sites")
+        d_text = d_off = None
+        if p.text is not None:
+            off = np.empty(R + 1, dtype=np.uint64)
+            off[:R] = p.rec_hdr
+            off[R] = int(p.text_bytes)
+            d_off = dev.alloc(off.nbytes)
+            bufs.append(d_off)
+            dev.upload(d_off, off)
+            d_text = p.text
+        d_nfix = dev.alloc(max(16, 4 * R))
+        bufs.append(d_nfix)
+        N.check(dev.ctx, N.lib().kman_apply_fixes(
+            dev.ctx, c_void_p(p.codes.ptr), n, c_void_p(d_fix.ptr), c_void_p(d_rec.ptr), R,
+            c_void_p(d_text.ptr) if d_text is not None else None, int(p.text_bytes) if d_text is not None else 0,
+            c_void_p(d_off.ptr) if d_off is not None else None, c_void_p(d_nfix.ptr)), "kman_apply_fixes")
+        return dev.download(d_nfix, R, np.uint32)
+    finally:
+        for b in bufs:
+            b.free()
+
+
 def _span_arrays(span, R: int):
     start, end = (np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1)) for a in span)
     if start.shape != (R,) or end.shape != (R,):
@@ -2164,13 +2223,15 @@ def screen_keep(stats: np.ndarray, min_hits: int = 0, min_frac: float = 0.0, inv
     return keep.astype(np.uint8)
 
 
-def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None, median=None, *, span=None):
+def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None, median=None, *, span=None, fixes=None):
     """The `kmer screen` text of screen()'s rows: one "name<TAB>windows<TAB>
     hits<TAB>sum" line per record with keep != 0 (None: all), in input order
     (kman_format_screen); with `median` (u32 per record) a fifth column
     "<TAB>median" (kman_format_screen_median); with `span` (solid_spans()'s
-    pair) two last columns "<TAB>START<TAB>END" (kman_format_screen_solid).
-    Returned, or written to the binary file `sink`."""
+    pair) two last columns "<TAB>START<TAB>END" (kman_format_screen_solid);
+    with `fixes` (correct()'s array; needs `span`) one more, "<TAB>FIXES"
+    (kman_format_screen_correct).  Returned, or written to the binary file
+    `sink`."""
     stats = np.asarray(stats, dtype=np.uint64).reshape(-1, 3)
     R = stats.shape[0]
     if R != p.n_records:
@@ -2187,6 +2248,17 @@ def emit_screen(p: Parsed, stats: np.ndarray, keep, sink=None, median=None, *, s
         median = np.ascontiguousarray(median, dtype=np.uint32)
         if median.shape != (R,):
             raise AssertionError("median array of %r for %d records" % (median.shape, R))
+    if fixes is not None:
+        if span is None:
+            raise AssertionError("fixes need the span arrays")
+        fixes = np.ascontiguousarray(fixes, dtype=np.uint32)
+        if fixes.shape != (R,):
+            raise AssertionError("fixes array of %r for %d records" % (fixes.shape, R))
+        start, end = _span_arrays(span, R)
+        mp = median.ctypes.data_as(c_void_p) if median is not None else None
+        return _to(sink, _format(N.lib().kman_format_screen_correct, planes.ctypes.data_as(c_void_p), mp,
+                                 start.ctypes.data_as(c_void_p), end.ctypes.data_as(c_void_p),
+                                 fixes.ctypes.data_as(c_void_p), R, kp, p.names_blob, off.ctypes.data_as(c_void_p)))
     if span is not None:
         start, end = _span_arrays(span, R)
         mp = median.ctypes.data_as(c_void_p) if median is not None else None

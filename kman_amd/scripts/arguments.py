@@ -225,6 +225,15 @@ def trim():
                              "Needs --solid, --reads-out and fastq READS")
 
 
+def correct():
+    return click.option("--correct", "correct", is_flag=True, default=False,
+                        help="Repair isolated substitution errors on the GPU before anything else is computed: a base "
+                             "covered by at most K k-mers in a row whose counts are below C, next to a k-mer with a "
+                             "count of at least C, is replaced when exactly one other base lifts all of them to C. "
+                             "Adds a last column FIXES; --reads-out then writes the corrected reads (fastq READS "
+                             "only). Needs --solid")
+
+
 def index_bits():
     return click.option("--index-bits", "index_bits", type=click.IntRange(1, 24), default=None,
                         help="Key bits of the table's prefix index (at most 2 K). Default: about 8 rows per bucket")

@@ -406,6 +406,15 @@ never compressed.  --trim cuts each of them to its solid stretch: the header
 line, the sequence columns [START, END), the "+" line and the same columns of
 the quality line, every line ended by "\n"; reads without a stretch are left
 out as --bed leaves them out; it needs --solid, --reads-out and fastq READS.
+--correct (with --solid C) first repairs isolated substitution errors on the
+GPU (kman_correct_sites, kman_apply_fixes): at most K k-mers in a row with a
+count below C, next to a k-mer with a count of at least C, name one base, and
+it is replaced when exactly one other base lifts every k-mer over it to C.
+Every column, --bed and every selection then describe the corrected reads, and
+one last column "<TAB>FIXES" counts the record's replaced bases; --reads-out
+writes the corrected records (fastq READS only; cut after the correction under
+--trim), quality values unchanged.  One pass: run the command on its output to
+correct again.
 Launched one process per GPU, the command runs on rank 0 alone.
 """)
 @args.reads_path()
@@ -429,19 +438,21 @@ Launched one process per GPU, the command runs on rank 0 alone.
 @args.bed()
 @args.reads_out()
 @args.trim()
+@args.correct()
 @args.index_bits()
 def screen(reads_path: str, table_input: str, output_path: str, k: int, canonical: bool = False,
            input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33", min_count: int = 1,
            max_count: Optional[int] = None, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False,
            index_bits: Optional[int] = None, median: bool = False, min_median: Optional[int] = None,
            max_median: Optional[int] = None, solid: Optional[int] = None, min_solid_len: Optional[int] = None,
-           bed_path: Optional[str] = None, reads_out: Optional[str] = None, trim: bool = False) -> None:
+           bed_path: Optional[str] = None, reads_out: Optional[str] = None, trim: bool = False,
+           correct: bool = False) -> None:
     input_file_exists(reads_path)
     input_file_exists(table_input)
     fastq = [_is_fastq(p, input_format) for p in (reads_path, table_input)]
     _check_screen_options(k, min_qual, fastq, min_count, max_count, min_hits, min_frac, index_bits, min_median,
                           max_median, solid, min_solid_len, bed_path, reads_out=reads_out, trim=trim,
-                          output_path=output_path)
+                          output_path=output_path, correct=correct)
     median = median or min_median is not None or max_median is not None
     if launch.distributed() and not launch.solo_rank():
         launch.log_solo("kmer screen")  # (the table and the reads on one GPU: DESIGN §8)
@@ -468,7 +479,9 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
             p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset),
                                   keep_text=True)
         try:
-            span = None
+            span = fixes = None
+            if correct:  # (then every step below reads the corrected codes, and --reads-out the corrected text)
+                fixes = engine.correct(p, table, canonical, solid, index_bits=index_bits)
             if solid is not None:
                 stats, med, runs = engine.screen_solid(p, table, canonical, solid, median=median,
                                                        index_bits=index_bits)
@@ -483,7 +496,10 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
                 stats, med = engine.screen(p, table, canonical, index_bits=index_bits), None
                 keep = engine.screen_keep(stats, min_hits, min_frac, invert)
             with open(output_path, "wb") as fh:
-                engine.emit_screen(p, stats, keep, fh, median=med, span=span)
+                if fixes is None:  # (today's call, today's bytes)
+                    engine.emit_screen(p, stats, keep, fh, median=med, span=span)
+                else:
+                    engine.emit_screen(p, stats, keep, fh, median=med, span=span, fixes=fixes)
             if bed_path is not None:
                 with open(bed_path, "wb") as fh:
                     engine.emit_bed(p, span, keep, fh)
@@ -502,7 +518,7 @@ def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_coun
                           max_median: Optional[int] = None, solid: Optional[int] = None,
                           min_solid_len: Optional[int] = None, bed_path: Optional[str] = None, *,
                           reads_out: Optional[str] = None, trim: bool = False,
-                          output_path: Optional[str] = None) -> None:
+                          output_path: Optional[str] = None, correct: bool = False) -> None:
     """What `kmer screen` refuses, before any device work or output."""
     if k <= 1:
         raise AssertionError("k must be >= 1, got %d instead." % k)
@@ -540,6 +556,11 @@ def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_coun
             raise AssertionError("--trim needs --reads-out")
         if not fastq[0]:
             raise AssertionError("--trim needs fastq READS")
+    if correct:
+        if solid is None:
+            raise AssertionError("--correct needs --solid")
+        if reads_out is not None and not fastq[0]:
+            raise AssertionError("--correct with --reads-out needs fastq READS")
     if reads_out is not None:
         if reads_out.endswith(".gz"):
             raise AssertionError("--reads-out writes plain text: %r ends in .gz" % reads_out)
