@@ -996,6 +996,51 @@ int kman_apply_fixes(kman_ctx *ctx, uint8_t *d_codes, uint64_t n_bases, const ui
                      const uint64_t *d_rec_seq, uint64_t n_records, uint8_t *d_text, uint64_t n_bytes,
                      const uint64_t *d_rec_off, uint32_t *d_nfix);
 
+/* ------------------------------------------------- two inputs, zipped by record
+ * Not in the reference: the codes of two parsed inputs whose i-th records are
+ * the two mates of pair i, interleaved by record in one buffer (`kmer screen
+ * --mate`, `kmer classify --mate`): mate 1 of pair 0, mate 2 of pair 0, mate 1
+ * of pair 1, ..  The lookup kernels cut windows at bit 3 of the codes and
+ * attribute them by the record table they are given: with every second entry
+ * of the zipped table they count per pair, with every entry per mate.
+ *
+ * kman_zip_records: d_codes1, n_bases1 and d_codes2, n_bases2: the codes of
+ *   the two inputs as the parsers write them (16-byte aligned).  d_rec_seq1,
+ *   d_rec_seq2: their record tables, n_records ascending first-base indices
+ *   each (equal neighbours are empty records; the last record runs to
+ *   n_bases).  Neither input is modified.
+ *   d_codes (16-byte aligned, room for n_bases1 + n_bases2 + 64 bytes) takes
+ *   the n_bases1 + n_bases2 codes, every byte copied verbatim (bit 3 and a
+ *   quality mask survive), then 64 pad bytes of value 4.  d_rec_seq takes
+ *   2 * n_records ascending entries: entry 2i is the first base of mate 1 of
+ *   pair i, entry 2i + 1 of its mate 2; an empty mate stays an empty record.
+ *   Bases before d_rec_seq1[0] or d_rec_seq2[0] belong to no record, as
+ *   everywhere: their places, at the front of d_codes, are written as 4.
+ *   n_records == 0 or no bases at all: only the pad is written (at d_codes;
+ *   with records and no bases d_rec_seq is all zeros).
+ *   A NULL d_codes, a NULL table with n_records > 0, NULL codes with bases, a
+ *   misaligned code buffer, more than 2^31 pairs: KMAN_EINVAL, nothing is
+ *   written.  A table that is not ascending or points past n_bases gives wrong
+ *   bytes, never a wild address or an endless loop: entries are clamped, a
+ *   source byte is read only below its n_bases, an output byte is written only
+ *   below n_bases1 + n_bases2 + 64, every search runs a step count fixed
+ *   before it starts.
+ *   The tables are the exclusive scans of the records' lengths already, so the
+ *   output offsets are sums of their entries: one thread per pair writes two.
+ *   The copy pass runs one block per KMAN_ZIP_TILE output bytes: the block
+ *   finds its slice of d_rec_seq by a block-wide search, stages it in LDS when
+ *   it has at most KMAN_ZIP_SEG_CAP segments and searches global memory
+ *   otherwise; an output word is one aligned 16-byte store, put together from
+ *   aligned 16-byte loads of the source of each mate that has bytes in it.
+ *   Every byte of d_codes has one writer.  n_bases1 + n_bases2 bytes are read
+ *   and as many written, 16 B of table per pair read and 16 B written.
+ *   Launches are timed under the tag "zip".  Synchronises. */
+#define KMAN_ZIP_TILE 16384
+#define KMAN_ZIP_SEG_CAP 1024
+int kman_zip_records(kman_ctx *ctx, const uint8_t *d_codes1, uint64_t n_bases1, const uint64_t *d_rec_seq1,
+                     const uint8_t *d_codes2, uint64_t n_bases2, const uint64_t *d_rec_seq2, uint64_t n_records,
+                     uint8_t *d_codes, uint64_t *d_rec_seq);
+
 /* kman_rebase_pos: uniq pos tagged with their source shard (bits 56-63) ->
  *   global pos: (pos & (2^56 - 1)) + (offsets[source] << 1), offsets = the
  *   global base index of each shard's first base (host array, nsrc <= 256).
@@ -1064,6 +1109,16 @@ int kman_format_screen_median(const uint64_t *out3, const uint32_t *median, uint
 int kman_format_screen_solid(const uint64_t *out3, const uint32_t *median, const uint64_t *start, const uint64_t *end,
                              uint64_t n_records, const uint8_t *keep, const char *names, const uint64_t *name_off,
                              char *buf, size_t cap, size_t *used, int threads);
+/* A pair's line (`kmer screen --mate --solid`): out3 and median hold one row
+ * per pair (kman_screen_records and kman_record_quantile with every second
+ * entry of kman_zip_records' table), start and end one row per mate, 2 *
+ * n_pairs each (kman_record_runs with every entry):
+ * "%s\t%llu\t%llu\t%llu[\t%u]\t%llu\t%llu\t%llu\t%llu\n" (name, windows, hits,
+ * sum, median[r] unless median == NULL, start[2r], end[2r], start[2r + 1],
+ * end[2r + 1]); names are the pairs'. */
+int kman_format_screen_pair(const uint64_t *out3, const uint32_t *median, const uint64_t *start, const uint64_t *end,
+                            uint64_t n_pairs, const uint8_t *keep, const char *names, const uint64_t *name_off,
+                            char *buf, size_t cap, size_t *used, int threads);
 /* kman_format_screen_solid's lines with the record's corrected bases as one
  * last column (`kmer screen --solid C --correct`):
  * "%s\t%llu\t%llu\t%llu[\t%u]\t%llu\t%llu\t%u\n" (.., start[r], end[r],

@@ -382,6 +382,47 @@ extern "C" int kman_format_screen_solid(const uint64_t *out3, const uint32_t *me
     return run_sliced(n_records, buf, cap, used, threads, size_of, write_at);
 }
 
+// a pair's line: the joint planes and median, then the solid span of mate 1
+// and of mate 2 (`kmer screen --mate --solid`); the span arrays hold the mates'
+// rows interleaved, 2 * n_pairs each
+extern "C" int kman_format_screen_pair(const uint64_t *out3, const uint32_t *median, const uint64_t *start,
+                                       const uint64_t *end, uint64_t n_pairs, const uint8_t *keep, const char *names,
+                                       const uint64_t *name_off, char *buf, size_t cap, size_t *used, int threads) {
+    if (!used || (n_pairs && (!out3 || !start || !end || !name_off))) return KMAN_EINVAL;
+    const uint64_t *w = out3, *h = out3 + n_pairs, *s = out3 + 2 * n_pairs;
+    auto size_of = [&](uint64_t r) -> size_t {
+        if (keep && !keep[r]) return 0;
+        return (name_off[r + 1] - name_off[r]) + 8 + ndigits(w[r]) + ndigits(h[r]) + ndigits(s[r]) +
+               (median ? 1 + ndigits(median[r]) : 0) + ndigits(start[2 * r]) + ndigits(end[2 * r]) +
+               ndigits(start[2 * r + 1]) + ndigits(end[2 * r + 1]);
+    };
+    auto write_at = [&](uint64_t r, char *p) -> char * {
+        if (keep && !keep[r]) return p;
+        const uint64_t L = name_off[r + 1] - name_off[r];
+        if (L) memcpy(p, names + name_off[r], L);
+        p += L;
+        *p++ = '\t';
+        p = put_u64(p, w[r]);
+        *p++ = '\t';
+        p = put_u64(p, h[r]);
+        *p++ = '\t';
+        p = put_u64(p, s[r]);
+        if (median) {
+            *p++ = '\t';
+            p = put_u64(p, median[r]);
+        }
+        for (uint64_t m = 2 * r; m < 2 * r + 2; m++) {
+            *p++ = '\t';
+            p = put_u64(p, start[m]);
+            *p++ = '\t';
+            p = put_u64(p, end[m]);
+        }
+        *p++ = '\n';
+        return p;
+    };
+    return run_sliced(n_pairs, buf, cap, used, threads, size_of, write_at);
+}
+
 // the same lines with the record's corrected bases as one last column
 // (`kmer screen --solid C --correct`)
 extern "C" int kman_format_screen_correct(const uint64_t *out3, const uint32_t *median, const uint64_t *start,

@@ -17,6 +17,7 @@ engine function        reference                                   kernel(s)
 ``sort``               Batch.sorted, batch.py:156-168              onesweep_pass x P
 ``count``              Crawler.do_batch + join_sequence_count      rle_count_kernel
 ``uniq``               Crawler.do_batch + join_unique              rle_uniq_kernel
+``zip_pairs``          (read pairs; not in the reference)          zip_offsets/zip_copy
 ``format_*``           join.py:262,284 / seq.py:489-495            host threads (C++)
 =====================  ==========================================  ============================
 """
@@ -202,6 +203,7 @@ class Parsed:
     n_masked: int = 0  # FASTQ with a quality threshold: the kept bytes below it (their codes read as N)
     text: Optional[DeviceBuffer] = None  # the input text on the device (text_bytes + 64), only with keep_text=True
     text_bytes: int = 0
+    mates: Optional[tuple] = None  # zip_pairs' result only: the two sources (codes freed, text kept), freed with it
 
     def record_of(self, base: int) -> int:
         return int(np.searchsorted(self.rec_seq, base, side="right")) - 1
@@ -211,6 +213,9 @@ class Parsed:
         if self.text is not None:
             self.text.free()
             self.text = None
+        if self.mates is not None:
+            for m in self.mates:
+                m.free()
 
 
 FORMATS = ("auto", "fasta", "fastq")
@@ -2425,6 +2430,281 @@ def emit_reads(p: Parsed, keep, sink, *, span=None, trim=False):
         off = list(p.rec_hdr) + [p.text_bytes]
         return _to(sink, _cut_host(text, off, keep, span, trim))
     return cut_records(p, keep, sink, span=span, trim=trim)
+
+
+# ------------------------------------------------------------------ read pairs
+#
+# Two views of one code buffer in which the mates of every pair are neighbours
+# (kman_zip_records, or an interleaved input as it is parsed): the MATE VIEW
+# has one record per mate, the PAIR VIEW one per pair, its table being every
+# second entry of the mate view's.  The lookup kernels cut windows at bit 3 of
+# the codes, so no window spans two mates in either view.
+
+
+class BorrowedBuffer:
+    """A device buffer that somebody else owns: ``ptr`` follows the owner's
+    (None once the owner freed it) and ``free`` does nothing, so a view can be
+    freed, or dropped, any number of times without touching the allocation."""
+
+    __slots__ = ("_owner",)
+
+    def __init__(self, owner: DeviceBuffer):
+        self._owner = owner
+
+    @property
+    def ptr(self):
+        return self._owner.ptr
+
+    @property
+    def nbytes(self) -> int:
+        return self._owner.nbytes
+
+    @property
+    def dev(self):
+        return self._owner.dev
+
+    def free(self) -> None:
+        pass
+
+    def offset(self, nbytes: int) -> int:
+        return self.ptr + int(nbytes)
+
+
+def _pair_keys(p: Parsed):
+    """(bytes, starts, lengths) of p's names by the pair name rule: a name is
+    ``Parsed.names[i]`` with one trailing ``/1`` or ``/2`` removed."""
+    arr = np.frombuffer(p.names_blob, dtype=np.uint8)
+    off = np.asarray(p.name_off, dtype=np.int64)
+    ln = off[1:] - off[:-1]
+    suf = np.zeros(len(ln), dtype=bool)
+    two = np.nonzero(ln >= 2)[0]
+    if len(two):
+        last, prev = arr[off[1:][two] - 1], arr[off[1:][two] - 2]
+        suf[two] = (prev == 0x2F) & ((last == 0x31) | (last == 0x32))
+    return arr, off[:-1], ln - 2 * suf
+
+
+def _first_name_mismatch(k1, k2) -> int:
+    """The first index at which two _pair_keys differ, -1 when none does."""
+    (a1, s1, l1), (a2, s2, l2) = k1, k2
+    bad = np.nonzero(l1 != l2)[0]
+    first = int(bad[0]) if len(bad) else len(l1)
+    ln = np.where(l1 == l2, l1, 0)
+    tot = int(ln.sum())
+    if tot:
+        base = np.cumsum(ln) - ln
+        within = np.arange(tot, dtype=np.int64) - np.repeat(base, ln)
+        diff = np.nonzero(a1[np.repeat(s1, ln) + within] != a2[np.repeat(s2, ln) + within])[0]
+        if len(diff):
+            first = min(first, int(np.searchsorted(base + ln, diff[0], side="right")))
+    return first if first < len(l1) else -1
+
+
+def check_pair_names(names1: Parsed, names2: Parsed) -> None:
+    """Refuses (AssertionError) the first pair whose two names differ by the
+    pair name rule (_pair_keys), naming the 1-based pair and both names.  Host
+    code over the parses' name blobs."""
+    i = _first_name_mismatch(_pair_keys(names1), _pair_keys(names2))
+    if i >= 0:
+        raise AssertionError("pair %d: the mates' names differ, %r and %r (a trailing /1 or /2 is ignored): the "
+                             "files are not in step" % (i + 1, bytes(names1.names[i]), bytes(names2.names[i])))
+
+
+def _even_names(p: Parsed):
+    """(names, blob, name_off) of the records 0, 2, 4, .. of p."""
+    arr = np.frombuffer(p.names_blob, dtype=np.uint8)
+    off = np.asarray(p.name_off, dtype=np.int64)
+    st, ln = off[:-1][0::2], (off[1:] - off[:-1])[0::2]
+    tot = int(ln.sum())
+    base = np.cumsum(ln) - ln
+    blob = arr[np.repeat(st, ln) + (np.arange(tot, dtype=np.int64) - np.repeat(base, ln))].tobytes() if tot else b""
+    name_off = np.zeros(len(ln) + 1, dtype=np.uint64)
+    if len(ln):
+        name_off[1:] = np.cumsum(ln, dtype=np.uint64)
+    return BlobNames(blob, name_off), blob, name_off
+
+
+def zip_pairs(p1: Parsed, p2: Parsed, *, check_names: bool = True) -> Parsed:
+    """The mate view of two parses whose i-th records are the two mates of pair
+    i (kman_zip_records): 2R records, record 2i mate 1 and record 2i + 1 mate 2
+    of pair i, their codes copied verbatim (bit 3, a ``-q`` mask) into one
+    fresh buffer.  Different record counts are refused, and with `check_names`
+    the first pair whose names differ (check_pair_names), both before any
+    device work.
+    ``p1.codes`` and ``p2.codes`` are freed once the zip is done (peak: twice
+    the codes).  Names, ``rec_hdr`` and the texts are not merged: the result
+    has no names, and carries the two sources as ``mates`` -- with their
+    names, ``rec_hdr`` and, when they were parsed with keep_text, their device
+    texts, for cut_records.  ``free()`` of the result frees them too; p1 and p2
+    must not be used for lookups afterwards."""
+    if p1.n_records != p2.n_records:
+        raise AssertionError("READS has %d records and READS2 has %d: the files are not the two ends of the same "
+                             "fragments" % (p1.n_records, p2.n_records))
+    if p1.dev is not p2.dev:
+        raise AssertionError("zip_pairs: the two parses are on different devices")
+    if check_names:
+        check_pair_names(p1, p2)
+    dev, R = p1.dev, int(p1.n_records)
+    n = int(p1.n_bases) + int(p2.n_bases) if R else 0
+    codes = d1 = d2 = d_out = None
+    try:
+        codes = dev.alloc(int(p1.n_bases) + int(p2.n_bases) + 64)
+        d1, d2, d_out = dev.alloc(max(16, 8 * R)), dev.alloc(max(16, 8 * R)), dev.alloc(max(16, 16 * R))
+        if R:
+            dev.upload(d1, np.ascontiguousarray(p1.rec_seq, dtype=np.uint64))
+            dev.upload(d2, np.ascontiguousarray(p2.rec_seq, dtype=np.uint64))
+        N.check(dev.ctx, N.lib().kman_zip_records(
+            dev.ctx, c_void_p(p1.codes.ptr), int(p1.n_bases), c_void_p(d1.ptr), c_void_p(p2.codes.ptr),
+            int(p2.n_bases), c_void_p(d2.ptr), R, c_void_p(codes.ptr), c_void_p(d_out.ptr)), "kman_zip_records")
+        rec_seq = dev.download(d_out, 2 * R, np.uint64)
+        res, codes = codes, None
+    finally:
+        for b in (codes, d1, d2, d_out):
+            if b is not None:
+                b.free()
+    p1.codes.free()
+    p2.codes.free()
+    phases.mark("zip_pairs")
+    return Parsed(dev, res, n, 2 * R, np.zeros(0, np.uint64), rec_seq, [], b"", np.zeros(1, np.uint64),
+                  int(p1.n_masked) + int(p2.n_masked), mates=(p1, p2))
+
+
+def pair_view(pz: Parsed) -> Parsed:
+    """The pair view of zip_pairs' result: the same codes with every second
+    entry of its record table, so R records, each a pair; names and
+    ``rec_hdr`` are mate 1's as READS has them.  The view borrows the codes
+    (BorrowedBuffer): freeing it frees nothing, and it is valid only while
+    `pz` is."""
+    if pz.mates is None:
+        raise AssertionError("pair_view takes zip_pairs' result; an interleaved parse goes to pairs_of")
+    p1 = pz.mates[0]
+    return Parsed(pz.dev, BorrowedBuffer(pz.codes), pz.n_bases, pz.n_records // 2, p1.rec_hdr,
+                  np.ascontiguousarray(pz.rec_seq[0::2]), p1.names, p1.names_blob, p1.name_off, pz.n_masked)
+
+
+def pairs_of(p: Parsed, *, check_names: bool = True) -> Parsed:
+    """The pair view of an ordinary parse of an interleaved input (records 2i
+    and 2i + 1 are the mates of pair i); `p` itself is the mate view.  No
+    kernel runs.  An odd record count is refused, and with `check_names` the
+    first pair whose two names differ (check_pair_names' rule).  Names and
+    ``rec_hdr`` are mate 1's.  The view borrows p's codes: freeing it frees
+    nothing."""
+    R2 = int(p.n_records)
+    if R2 % 2:
+        raise AssertionError("%d records: an interleaved input holds the two mates of every pair, an even number"
+                             % R2)
+    if check_names:
+        a, s, ln = _pair_keys(p)
+        i = _first_name_mismatch((a, s[0::2], ln[0::2]), (a, s[1::2], ln[1::2]))
+        if i >= 0:
+            raise AssertionError("pair %d: the mates' names differ, %r and %r (a trailing /1 or /2 is ignored): the "
+                                 "input is not interleaved" % (i + 1, bytes(p.names[2 * i]), bytes(p.names[2 * i + 1])))
+    names, blob, name_off = _even_names(p)
+    return Parsed(p.dev, BorrowedBuffer(p.codes), p.n_bases, R2 // 2, np.ascontiguousarray(p.rec_hdr[0::2]),
+                  np.ascontiguousarray(p.rec_seq[0::2]), names, blob, name_off, p.n_masked)
+
+
+def screen_pairs(pm: Parsed, pv: Parsed, table: CountResult, canonical: bool = False, *, median: bool = False,
+                 min_count: Optional[int] = None, index: Optional[DeviceBuffer] = None,
+                 index_bits: Optional[int] = None):
+    """(stats, median or None, runs or None) of read pairs: `pm` the mate view
+    and `pv` the pair view of the same codes.  stats: screen()'s rows per pair,
+    joint over both mates' windows; median (`median`): record_quantile's lower
+    median of the union of both mates' window counts, per pair; runs
+    (`min_count`): record_runs' rows per MATE, 2R of them.  kman_window_counts
+    runs once and serves both; the runs are taken first because the quantile
+    leaves the words as scratch.  Each k-mer is looked up once per kernel."""
+    if table.k > MAX_K:
+        raise AssertionError("screen takes k <= %d (one 64-bit key per k-mer), got %d" % (MAX_K, table.k))
+    if pm.codes.ptr != pv.codes.ptr or pm.n_records != 2 * pv.n_records:
+        raise AssertionError("screen_pairs: the two views are not of the same codes")
+    if min_count is not None:
+        min_count = _check_min_count(min_count)
+    bits = default_index_bits(table.n, table.k) if index_bits is None else _check_index_bits(index_bits, table.k)
+    own = d_wc = None
+    try:
+        if index is None:
+            index = own = table_index(pm.dev, table, bits)
+        stats = screen(pv, table, canonical, index=index, index_bits=bits)
+        med = runs = None
+        if median or min_count is not None:
+            d_wc = window_counts(pm, table, canonical, index=index, index_bits=bits)
+            if min_count is not None:
+                runs = record_runs(pm, d_wc, min_count)
+            if median:
+                med = record_quantile(pv, d_wc)
+        return stats, med, runs
+    finally:
+        for b in (own, d_wc):
+            if b is not None:
+                b.free()
+
+
+def pair_min_span(span):
+    """The mates' spans (2R rows, solid_spans of the mate view) as one span
+    per pair for screen_keep's ``min_solid_len``: (0, the shorter of the two
+    stretches), so a pair passes when both stretches do."""
+    start, end = (np.asarray(a, dtype=np.uint64).reshape(-1) for a in span)
+    ln = end - np.minimum(start, end)
+    m = np.minimum(ln[0::2], ln[1::2])
+    return np.zeros(len(m), np.uint64), np.ascontiguousarray(m)
+
+
+def emit_screen_pairs(pv: Parsed, stats: np.ndarray, keep, sink=None, median=None, *, span=None):
+    """The `kmer screen` text of read pairs: emit_screen's lines with one line
+    per pair of the pair view `pv` (the name is mate 1's); with `span` (the
+    mates' solid_spans, 2R rows) four last columns "<TAB>START<TAB>END<TAB>
+    START2<TAB>END2", mate 1's stretch and mate 2's (kman_format_screen_pair).
+    Returned, or written to the binary file `sink`."""
+    if span is None:
+        return emit_screen(pv, stats, keep, sink, median=median)
+    stats = np.asarray(stats, dtype=np.uint64).reshape(-1, 3)
+    R = stats.shape[0]
+    if R != pv.n_records:
+        raise AssertionError("%d rows for %d pairs" % (R, pv.n_records))
+    planes = np.ascontiguousarray(stats.T)
+    off = np.ascontiguousarray(pv.name_off, dtype=np.uint64)
+    keep = _keep_array(keep, R)
+    kp = keep.ctypes.data_as(c_void_p) if keep is not None else None
+    mp = None
+    if median is not None:
+        median = np.ascontiguousarray(median, dtype=np.uint32)
+        if median.shape != (R,):
+            raise AssertionError("median array of %r for %d pairs" % (median.shape, R))
+        mp = median.ctypes.data_as(c_void_p)
+    start, end = _span_arrays(span, 2 * R)
+    return _to(sink, _format(N.lib().kman_format_screen_pair, planes.ctypes.data_as(c_void_p), mp,
+                             start.ctypes.data_as(c_void_p), end.ctypes.data_as(c_void_p), R, kp, pv.names_blob,
+                             off.ctypes.data_as(c_void_p)))
+
+
+def emit_pair_reads(pm: Parsed, keep, sink1, sink2=None, *, span=None, trim=False):
+    """`--reads-out` for read pairs: the listed pairs' records, both mates of a
+    pair or neither.  `pm` is the mate view: zip_pairs' result (the mates'
+    texts are cut into `sink1` and `sink2`, both calls of cut_records with the
+    same keep array, so record i of one file and record i of the other are
+    mates), or an interleaved parse (one interleaved text into `sink1`, the
+    pair's flag applied to both of its records).  Under `trim` (`span`: the
+    mates' solid_spans, 2R rows) each mate is cut to its own stretch and a pair
+    with a mate that has no stretch is left out whole."""
+    R = int(pm.n_records) // 2
+    keep = _keep_array(keep, R)
+    keep = np.ones(R, np.uint8) if keep is None else keep.copy()
+    if trim:
+        if span is None:
+            raise AssertionError("trim needs the span arrays")
+        start, end = _span_arrays(span, 2 * R)
+        has = end > start
+        keep[~(has[0::2] & has[1::2])] = 0
+    if pm.mates is None:
+        if sink2 is not None:
+            raise AssertionError("an interleaved input is written to one file")
+        return emit_reads(pm, np.repeat(keep, 2), sink1, span=(start, end) if trim else None, trim=trim)
+    if sink2 is None:
+        raise AssertionError("two inputs are written to two files")
+    for m, sink, sl in ((pm.mates[0], sink1, slice(0, None, 2)), (pm.mates[1], sink2, slice(1, None, 2))):
+        sp = (np.ascontiguousarray(start[sl]), np.ascontiguousarray(end[sl])) if trim else None
+        emit_reads(m, keep, sink, span=sp, trim=trim)
 
 
 # ------------------------------------------------- reads among references (classify)

@@ -218,6 +218,29 @@ def reads_out():
                              "that ends in .gz is refused")
 
 
+def mate():
+    return click.option("--mate", "-2", "mate_path", metavar="READS2", default=None,
+                        type=click.Path(exists=True, file_okay=True, readable=True),
+                        help="The second ends of the reads: record i of READS2 is the mate of record i of READS "
+                             "(same format, same number of records, same names but for a trailing /1 or /2). "
+                             "Every line, every selection and every label is then one per pair, joint over "
+                             "both mates' k-mers")
+
+
+def interleaved():
+    return click.option("--interleaved", "interleaved", is_flag=True, default=False,
+                        help="READS holds read pairs interleaved: records 2i and 2i+1 are the two mates of pair i. "
+                             "As --mate, with one input and one --reads-out file. Not with --mate")
+
+
+def reads_out2():
+    return click.option("--reads-out2", "reads_out2", type=click.Path(dir_okay=False, writable=True), default=None,
+                        metavar="FILE",
+                        help="With --mate: the written pairs' second mates, from READS2, as --reads-out writes the "
+                             "first mates from READS; record i of the two files are always mates. Needs --mate "
+                             "and --reads-out")
+
+
 def trim():
     return click.option("--trim", "trim", is_flag=True, default=False,
                         help="Cut every read of --reads-out to its solid stretch: sequence and quality columns "

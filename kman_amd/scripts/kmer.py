@@ -415,6 +415,21 @@ one last column "<TAB>FIXES" counts the record's replaced bases; --reads-out
 writes the corrected records (fastq READS only; cut after the correction under
 --trim), quality values unchanged.  One pass: run the command on its output to
 correct again.
+--mate READS2 (-2) reads paired files, record i of READS2 the mate of record i
+of READS (same record count; same names, a trailing /1 or /2 aside);
+--interleaved reads the pairs from READS alone, mates as neighbours.  The
+mates' bases are interleaved on the GPU (kman_zip_records) and every k-mer is
+looked up once: OUTPUT has one line per pair, NAME mate 1's, and K-MERS, HITS,
+SUM and MEDIAN are joint over both mates' k-mers (no k-mer spans the mates);
+--min-hits, --min-frac, -v, --min-median and --max-median select pairs.
+--solid C then writes "START<TAB>END<TAB>START2<TAB>END2", each mate's own
+stretch, and --min-solid-len N keeps a pair when both stretches have N bases.
+--reads-out FILE with --reads-out2 FILE2 (both or neither) writes the written
+pairs' mates from READS and from READS2: record i of FILE and of FILE2 are
+always mates, a pair is kept or dropped whole; --trim cuts each mate to its own
+stretch and leaves out a pair with a mate that has none.  Under --interleaved
+--reads-out writes one interleaved file.  Pairs take neither --bed nor
+--correct, and READS and READS2 must both be fastq or both be fasta.
 Launched one process per GPU, the command runs on rank 0 alone.
 """)
 @args.reads_path()
@@ -439,6 +454,9 @@ Launched one process per GPU, the command runs on rank 0 alone.
 @args.reads_out()
 @args.trim()
 @args.correct()
+@args.mate()
+@args.interleaved()
+@args.reads_out2()
 @args.index_bits()
 def screen(reads_path: str, table_input: str, output_path: str, k: int, canonical: bool = False,
            input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33", min_count: int = 1,
@@ -446,13 +464,19 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
            index_bits: Optional[int] = None, median: bool = False, min_median: Optional[int] = None,
            max_median: Optional[int] = None, solid: Optional[int] = None, min_solid_len: Optional[int] = None,
            bed_path: Optional[str] = None, reads_out: Optional[str] = None, trim: bool = False,
-           correct: bool = False) -> None:
+           correct: bool = False, mate_path: Optional[str] = None, interleaved: bool = False,
+           reads_out2: Optional[str] = None) -> None:
     input_file_exists(reads_path)
     input_file_exists(table_input)
     fastq = [_is_fastq(p, input_format) for p in (reads_path, table_input)]
+    fastq_mate = None
+    if mate_path is not None:
+        input_file_exists(mate_path)
+        fastq_mate = _is_fastq(mate_path, input_format)
     _check_screen_options(k, min_qual, fastq, min_count, max_count, min_hits, min_frac, index_bits, min_median,
                           max_median, solid, min_solid_len, bed_path, reads_out=reads_out, trim=trim,
-                          output_path=output_path, correct=correct)
+                          output_path=output_path, correct=correct, mate_path=mate_path, interleaved=interleaved,
+                          reads_out2=reads_out2, fastq_mate=fastq_mate)
     median = median or min_median is not None or max_median is not None
     if launch.distributed() and not launch.solo_rank():
         launch.log_solo("kmer screen")  # (the table and the reads on one GPU: DESIGN §8)
@@ -473,6 +497,12 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
             ranged = engine.filtered_copy(dev, table, min_count, max_count)
             engine.free_result(table)
             table = ranged
+        if mate_path is not None or interleaved:
+            _screen_pairs(dev, table, reads_path, mate_path, output_path, canonical, input_format,
+                          min_qual if fastq[0] else 0, int(phred_offset), min_hits, min_frac, invert, index_bits,
+                          median, min_median, max_median, solid, min_solid_len, reads_out, reads_out2, trim)
+            logging.info("That's all!")
+            return
         if reads_out is None:  # (not one allocation or call differs from a run without the option)
             p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset))
         else:
@@ -513,13 +543,91 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
     logging.info("That's all!")
 
 
+def _parse_pairs(dev, reads_path: str, mate_path: Optional[str], input_format: str, min_qual: int,
+                 phred_offset: int, keep_text: bool):
+    """(mate view, pair view) of READS and READS2 (zipped on the GPU), or of an
+    interleaved READS alone (`mate_path` None).  Freeing the mate view frees
+    everything; the pair view borrows its codes."""
+    p1 = engine.parse_file(dev, reads_path, input_format, min_qual, phred_offset, keep_text=keep_text)
+    if mate_path is None:
+        try:
+            return p1, engine.pairs_of(p1)
+        except BaseException:
+            p1.free()
+            raise
+    p2 = None
+    try:
+        p2 = engine.parse_file(dev, mate_path, input_format, min_qual, phred_offset, keep_text=keep_text)
+        pm = engine.zip_pairs(p1, p2)
+    except BaseException:
+        p1.free()
+        if p2 is not None:
+            p2.free()
+        raise
+    return pm, engine.pair_view(pm)
+
+
+def _screen_pairs(dev, table, reads_path: str, mate_path: Optional[str], output_path: str, canonical: bool,
+                  input_format: str, min_qual: int, phred_offset: int, min_hits: int, min_frac: float, invert: bool,
+                  index_bits: Optional[int], median: bool, min_median: Optional[int], max_median: Optional[int],
+                  solid: Optional[int], min_solid_len: Optional[int], reads_out: Optional[str],
+                  reads_out2: Optional[str], trim: bool) -> None:
+    """`kmer screen --mate` / `--interleaved`: one line per pair, the listed
+    pairs' records in step."""
+    pm, pv = _parse_pairs(dev, reads_path, mate_path, input_format, min_qual, phred_offset, reads_out is not None)
+    try:
+        stats, med, runs = engine.screen_pairs(pm, pv, table, canonical, median=median, min_count=solid,
+                                               index_bits=index_bits)
+        span = engine.solid_spans(runs, table.k) if runs is not None else None
+        keep = engine.screen_keep(stats, min_hits, min_frac, invert, median=med, min_median=min_median,
+                                  max_median=max_median, span=engine.pair_min_span(span) if span is not None else None,
+                                  min_solid_len=min_solid_len)
+        with open(output_path, "wb") as fh:
+            engine.emit_screen_pairs(pv, stats, keep, fh, median=med, span=span)
+        if reads_out is not None and reads_out2 is not None:
+            with open(reads_out, "wb") as f1, open(reads_out2, "wb") as f2:
+                engine.emit_pair_reads(pm, keep, f1, f2, span=span if trim else None, trim=trim)
+        elif reads_out is not None:
+            with open(reads_out, "wb") as fh:
+                engine.emit_pair_reads(pm, keep, fh, span=span if trim else None, trim=trim)
+    finally:
+        pm.free()
+
+
 def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_count: Optional[int], min_hits: int,
                           min_frac: float, index_bits: Optional[int], min_median: Optional[int] = None,
                           max_median: Optional[int] = None, solid: Optional[int] = None,
                           min_solid_len: Optional[int] = None, bed_path: Optional[str] = None, *,
                           reads_out: Optional[str] = None, trim: bool = False,
-                          output_path: Optional[str] = None, correct: bool = False) -> None:
+                          output_path: Optional[str] = None, correct: bool = False,
+                          mate_path: Optional[str] = None, interleaved: bool = False,
+                          reads_out2: Optional[str] = None, fastq_mate: Optional[bool] = None) -> None:
     """What `kmer screen` refuses, before any device work or output."""
+    if mate_path is not None and interleaved:
+        raise AssertionError("--mate and --interleaved exclude each other: the pairs are in two files or in one")
+    if reads_out2 is not None and mate_path is None:
+        raise AssertionError("--reads-out2 needs --mate: it takes the second mates from READS2%s"
+                             % (" (--interleaved writes one interleaved --reads-out file)" if interleaved else ""))
+    if mate_path is not None or interleaved:
+        if bed_path is not None:
+            raise AssertionError("--bed is not offered for read pairs: one region file for two read files is "
+                                 "ambiguous")
+        if correct:
+            raise AssertionError("--correct is not offered for read pairs: applying the fixes to two source texts "
+                                 "is a later change")
+    if mate_path is not None:
+        if fastq_mate is not None and bool(fastq_mate) != bool(fastq[0]):
+            raise AssertionError("READS is %s and READS2 is %s: mixed formats are not offered, both must be fastq or "
+                                 "both fasta" % tuple("fastq" if f else "fasta" for f in (fastq[0], fastq_mate)))
+        if (reads_out is None) != (reads_out2 is None):
+            raise AssertionError("with --mate, --reads-out and --reads-out2 go together (both or neither): a pair is "
+                                 "written to two files that stay in step")
+    if reads_out2 is not None:
+        if reads_out2.endswith(".gz"):
+            raise AssertionError("--reads-out2 writes plain text: %r ends in .gz" % reads_out2)
+        for name, other in (("OUTPUT", output_path), ("--reads-out", reads_out)):
+            if other is not None and _same_path(reads_out2, other):
+                raise AssertionError("--reads-out2 and %s name the same file, %r" % (name, reads_out2))
     if k <= 1:
         raise AssertionError("k must be >= 1, got %d instead." % k)
     if k > engine.MAX_K:
@@ -600,6 +708,15 @@ reference (its k-mers after -L / -U, the records assigned to it), then
 records themselves to P.LABEL.fq (.fa for fasta READS) per reference,
 P.ambiguous.* and P.unassigned.*, byte for byte as READS has them, cut out on
 the GPU (kman_cut_records) and never compressed.
+--mate READS2 (-2) reads paired files, record i of READS2 the mate of record i
+of READS (same record count; same names, a trailing /1 or /2 aside; both fastq
+or both fasta); --interleaved reads the pairs from READS alone, mates as
+neighbours.  The mates' bases are interleaved on the GPU (kman_zip_records)
+and a pair gets ONE label, from the k-mers of both mates: OUTPUT has one line
+per pair (NAME mate 1's), --hits and --summary count pairs.
+--reads-out-prefix then writes P.LABEL.1.fq from READS and P.LABEL.2.fq from
+READS2 (record i of the two are always mates), under --interleaved one
+interleaved P.LABEL.fq.
 Launched one process per GPU, the command runs on rank 0 alone.
 """)
 @args.reads_path()
@@ -619,12 +736,14 @@ Launched one process per GPU, the command runs on rank 0 alone.
 @args.hits()
 @args.summary()
 @args.reads_out_prefix()
+@args.mate()
+@args.interleaved()
 @args.index_bits()
 def classify(reads_path: str, output_path: str, k: int, refs=(), canonical: bool = False, input_format: str = "auto",
              min_qual: int = 0, phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None,
              specific: bool = False, min_hits: int = 1, min_frac: float = 0.0, min_margin: int = 1,
              hits: bool = False, summary_path: Optional[str] = None, reads_out_prefix: Optional[str] = None,
-             index_bits: Optional[int] = None) -> None:
+             index_bits: Optional[int] = None, mate_path: Optional[str] = None, interleaved: bool = False) -> None:
     input_file_exists(reads_path)
     refs = list(refs)
     for path in refs:
@@ -632,7 +751,14 @@ def classify(reads_path: str, output_path: str, k: int, refs=(), canonical: bool
     fastq = [_is_fastq(p, input_format) for p in [reads_path] + refs]
     labels = [ref_label(path) for path in refs]
     ext = "fq" if fastq[0] else "fa"
-    outs = _classify_outputs(reads_out_prefix, labels, ext)
+    paired = mate_path is not None or interleaved
+    if paired:
+        _check_pair_inputs(mate_path, interleaved, fastq[0], input_format)
+    if mate_path is not None:  # (two files per class)
+        pair_outs = _classify_pair_outputs(reads_out_prefix, labels, ext)
+        outs = [(o[0], path) for o in pair_outs for path in o[1:]]
+    else:
+        outs = pair_outs = _classify_outputs(reads_out_prefix, labels, ext)
     _check_classify_options(k, labels, min_qual, fastq, min_count, max_count, min_hits, min_frac, min_margin,
                             index_bits, output_path, summary_path, outs)
     if launch.distributed() and not launch.solo_rank():
@@ -661,6 +787,12 @@ def classify(reads_path: str, output_path: str, k: int, refs=(), canonical: bool
         ctable = engine.color_table(dev, tables)  # (frees each table as it is folded in)
         index = engine.table_index(dev, ctable, index_bits)
         try:
+            if paired:
+                _classify_pairs(dev, ctable, nc, index, reads_path, mate_path, output_path, canonical, specific,
+                                input_format, min_qual if fastq[0] else 0, int(phred_offset), min_hits, min_frac,
+                                min_margin, hits, summary_path, labels, table_kmers, pair_outs, index_bits)
+                logging.info("That's all!")
+                return
             p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset),
                                   keep_text=reads_out_prefix is not None)
             try:
@@ -686,6 +818,56 @@ def classify(reads_path: str, output_path: str, k: int, refs=(), canonical: bool
             engine.free_result(t)
         engine.free_result(ctable)
     logging.info("That's all!")
+
+
+def _classify_pairs(dev, ctable, nc: int, index, reads_path: str, mate_path: Optional[str], output_path: str,
+                    canonical: bool, specific: bool, input_format: str, min_qual: int, phred_offset: int,
+                    min_hits: int, min_frac: float, min_margin: int, hits: bool, summary_path: Optional[str], labels,
+                    table_kmers, pair_outs, index_bits: Optional[int]) -> None:
+    """`kmer classify --mate` / `--interleaved`: one label and one line per
+    pair, the classes' records in step."""
+    pm, pv = _parse_pairs(dev, reads_path, mate_path, input_format, min_qual, phred_offset, bool(pair_outs))
+    try:
+        res = engine.classify(pv, ctable, nc, canonical, specific, index=index, index_bits=index_bits, planes=hits)
+        windows, best, nhits, second = res[:4]
+        assign = engine.classify_assign(windows, best, nhits, second, min_hits, min_frac, min_margin)
+        with open(output_path, "wb") as fh:
+            engine.emit_classify(pv, labels, windows, assign, nhits, second, fh, planes=res[4] if hits else None)
+        if summary_path is not None:
+            with open(summary_path, "wb") as fh:
+                fh.write(classify_summary(labels, table_kmers, assign))
+        for out in pair_outs:
+            keep = (assign == out[0]).astype("uint8")
+            if len(out) == 3:
+                with open(out[1], "wb") as f1, open(out[2], "wb") as f2:
+                    engine.emit_pair_reads(pm, keep, f1, f2)
+            else:
+                with open(out[1], "wb") as fh:
+                    engine.emit_pair_reads(pm, keep, fh)
+    finally:
+        pm.free()
+
+
+def _check_pair_inputs(mate_path: Optional[str], interleaved: bool, fastq_reads: bool, input_format: str) -> None:
+    """What `kmer classify` refuses of --mate / --interleaved, before any device work."""
+    if mate_path is not None and interleaved:
+        raise AssertionError("--mate and --interleaved exclude each other: the pairs are in two files or in one")
+    if mate_path is not None:
+        input_file_exists(mate_path)
+        fastq_mate = _is_fastq(mate_path, input_format)
+        if bool(fastq_mate) != bool(fastq_reads):
+            raise AssertionError("READS is %s and READS2 is %s: mixed formats are not offered, both must be fastq or "
+                                 "both fasta" % tuple("fastq" if f else "fasta" for f in (fastq_reads, fastq_mate)))
+
+
+def _classify_pair_outputs(prefix: Optional[str], labels, ext: str):
+    """(assignment value, path of the first mates, path of the second mates) of
+    every --reads-out-prefix class under --mate."""
+    if prefix is None:
+        return []
+    names = [(c, lab) for c, lab in enumerate(labels)] + [(engine.AMBIGUOUS, "ambiguous"),
+                                                          (engine.UNASSIGNED, "unassigned")]
+    return [(c, "%s.%s.1.%s" % (prefix, lab, ext), "%s.%s.2.%s" % (prefix, lab, ext)) for c, lab in names]
 
 
 RESERVED_LABELS = ("-", "?", "ambiguous", "unassigned")
