@@ -1041,6 +1041,47 @@ int kman_zip_records(kman_ctx *ctx, const uint8_t *d_codes1, uint64_t n_bases1, 
                      const uint8_t *d_codes2, uint64_t n_bases2, const uint64_t *d_rec_seq2, uint64_t n_records,
                      uint8_t *d_codes, uint64_t *d_rec_seq);
 
+/* ------------------------------------------------ homopolymer-compressed codes
+ * Not in the reference: every run of one base collapsed to its first base
+ * before k-mers are taken (`--hpc`; minimap2 -H, meryl compress), a segmented
+ * stream compaction over one byte per base.
+ *
+ * kman_hpc_records: d_codes, n_bases: codes as the parsers write them (bits
+ *   0-1 the base, bit 2 not-ACGT, bit 3 a record's first character; 16-byte
+ *   aligned).  Base i is DROPPED exactly when i > 0, bits 2 and 3 of code[i]
+ *   are clear and (code[i - 1] & 7) == (code[i] & 7); every other byte is kept
+ *   verbatim.  So a record's first base is always kept and no run crosses a
+ *   record boundary, N and other not-ACGT characters are never dropped, a base
+ *   masked by -q separates the bases on its two sides, and bases before
+ *   d_rec_seq[0] follow the same rule.
+ *   d_rec_seq: n_records ascending first-base indices (entries are clamped to
+ *   n_bases).  d_out_codes (16-byte aligned, room for n_bases + 64 bytes; not
+ *   d_codes, nor overlapping it): the kept codes in order, then 64 bytes of
+ *   value 4.  d_out_rec_seq[r]: the kept bases with an original index <
+ *   d_rec_seq[r] (empty records stay empty records).  d_orig (may be NULL;
+ *   room for n_bases u64): the original index of kept base j.  *n_out: the
+ *   kept bases.  n_bases == 0: only the pad is written, the table is zeros.
+ *   A NULL or misaligned buffer, or d_out_codes over d_codes: KMAN_EINVAL,
+ *   nothing written.  A table that is not ascending gives wrong numbers,
+ *   never a wild address nor an unbounded loop: every record is looked up on
+ *   its own, in a fixed number of steps.
+ *   One block per KMAN_HPC_TILE input bytes: 16-byte loads, the predecessor
+ *   of a wave's first byte read from d_codes, keep flags by byte-parallel
+ *   arithmetic, ranks by one packed DPP wave scan, the tile's offset from the
+ *   decoupled look-back; the kept bytes are staged in LDS at the output's
+ *   alignment and stored as aligned 16-byte words (the words that two tiles
+ *   share byte by byte: every output byte has one writer).  A second kernel,
+ *   one thread per record, adds the kept bytes between the record's
+ *   KMAN_HPC_GROUP-byte boundary (whose prefix the first kernel noted) and its
+ *   first base.  n_bases bytes are read and *n_out written, 8 B per kept base
+ *   more with d_orig, 8 B per KMAN_HPC_GROUP input bytes of prefixes.
+ *   Launches are timed under the tag "hpc".  Synchronises. */
+#define KMAN_HPC_TILE 8192
+#define KMAN_HPC_GROUP 256
+int kman_hpc_records(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases, const uint64_t *d_rec_seq,
+                     uint64_t n_records, uint8_t *d_out_codes, uint64_t *d_out_rec_seq, uint64_t *d_orig,
+                     uint64_t *n_out);
+
 /* kman_rebase_pos: uniq pos tagged with their source shard (bits 56-63) ->
  *   global pos: (pos & (2^56 - 1)) + (offsets[source] << 1), offsets = the
  *   global base index of each shard's first base (host array, nsrc <= 256).

@@ -56,6 +56,7 @@ KMAN_CUT_TILE = 16384  # output bytes per block of kman_cut_records' copy pass
 KMAN_CUT_SEG_CAP = 1024  # segments of a tile staged in LDS; more: searched in global memory
 KMAN_ZIP_TILE = 16384  # output bytes per block of kman_zip_records' copy pass (include/kman.h)
 KMAN_ZIP_SEG_CAP = 1024  # segments (mates) of a tile staged in LDS; more: searched in global memory
+KMAN_HPC_TILE = 8192  # input bytes per block of kman_hpc_records (include/kman.h)
 KMAN_FIX_NONE = 0xFF  # kman_correct_sites: no correction at this base (include/kman.h)
 KMAN_CORRECT_TILE = 4096  # bases per tile of kman_correct_sites
 KMAN_CORRECT_REC_CAP = 512  # rec_seq entries of a tile staged in LDS; more: searched in global memory
@@ -289,6 +290,9 @@ SIGNATURES = {
     ),
     "kman_zip_records": (
         c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p],
+    ),
+    "kman_hpc_records": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)],
     ),
     "kman_format_screen_pair": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_char_p, c_void_p, c_void_p, c_size_t,

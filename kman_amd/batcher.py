@@ -151,8 +151,9 @@ class FastaBatcher(BatcherThreading):
                  size: int = BatcherThreading.DEFAULT_BATCH_SIZE, natype: NATYPES = BatcherThreading.DEFAULT_NATYPE,
                  tmp: Optional[str] = None, device: Optional[engine.Device] = None,
                  distributed: Optional[bool] = None, fmt: str = "auto", min_qual: int = 0,
-                 phred_offset: int = 33):
+                 phred_offset: int = 33, hpc: bool = False):
         super().__init__(size, threads, natype, tmp if tmp is not None else tempfile.gettempdir())
+        self.hpc = bool(hpc)  # homopolymer-compressed k-mers (engine.hpc): one GPU, the whole input
         if fmt not in engine.FORMATS:
             raise AssertionError("format must be one of %s, got %r" % (", ".join(engine.FORMATS), fmt))
         self.fmt = fmt  # input format: "auto" (engine.sniff_format), "fasta" or "fastq"
@@ -203,6 +204,8 @@ class FastaBatcher(BatcherThreading):
         engine._check_qual_format(self._qbyte, fmt)  # (before any device work)
         dev = self._device or engine.default_device()
         dist = launch.distributed() if self._distributed is None else self._distributed
+        if dist and self.hpc:
+            raise AssertionError("homopolymer compression runs on one GPU (rank 0 alone under a launch)")
         if dist and k <= engine.MAX_K and fmt != "fastq":  # (the byte-range shards cut FASTA only)
             # this rank's byte range only; ONE batch of its windows, joined
             # across the ranks by KJoiner.join (the batch cut does not change
@@ -212,8 +215,9 @@ class FastaBatcher(BatcherThreading):
             n = src.n_kmers
             self.feed_collection([Batch.from_source(src, 0, n, max(1, n), self.tmp)], feedMode)
             return self
+        kw = {"hpc": True} if self.hpc else {}
         src = FastaSource(dev, None, k, self.doReverseComplement, path=fasta, fmt=fmt, min_qual=self.min_qual,
-                          phred_offset=self.phred_offset)
+                          phred_offset=self.phred_offset, **kw)
         self.source = src
         if fmt == "fastq":  # (reads: millions of records, one line for all)
             logging.info("Batching %d reads..." % src.parsed.n_records)

@@ -204,6 +204,11 @@ class Parsed:
     text: Optional[DeviceBuffer] = None  # the input text on the device (text_bytes + 64), only with keep_text=True
     text_bytes: int = 0
     mates: Optional[tuple] = None  # zip_pairs' result only: the two sources (codes freed, text kept), freed with it
+    # hpc(keep_map=True)'s result only: the original index of every kept base (u64, on the device) and the
+    # record table and base count of the codes before the compression
+    hpc_orig: Optional[DeviceBuffer] = None
+    hpc_rec_seq: Optional[np.ndarray] = None
+    hpc_n_bases: int = 0
 
     def record_of(self, base: int) -> int:
         return int(np.searchsorted(self.rec_seq, base, side="right")) - 1
@@ -216,6 +221,9 @@ class Parsed:
         if self.mates is not None:
             for m in self.mates:
                 m.free()
+        if self.hpc_orig is not None:
+            self.hpc_orig.free()
+            self.hpc_orig = None
 
 
 FORMATS = ("auto", "fasta", "fastq")
@@ -1459,16 +1467,19 @@ def count_groups(p: Parsed, k: int, rc: bool = False, canonical: bool = False, o
 
 def abundance_hist(text: bytes, k: int, canonical: bool = True, nbins: int = 10001,
                    dev: Optional[Device] = None, fmt: str = "auto", min_qual: int = 0,
-                   phred_offset: int = 33) -> np.ndarray:
+                   phred_offset: int = 33, hpc: bool = False) -> np.ndarray:
     """k-mer abundance spectrum (BASELINE config 5; SURVEY §8f-1, not in the
     reference): h[c] = distinct (canonical) k-mers seen c times, h[-1] every
     count >= nbins - 1 (kman_count_hist over the count output).  `min_qual`,
-    `phred_offset`: parse_fastq's quality threshold."""
+    `phred_offset`: parse_fastq's quality threshold; `hpc`: homopolymer-compressed
+    k-mers (hpc() right after the parse)."""
     _check_k(k, wide=True)
     _check_qual_format(_qual_byte(min_qual, phred_offset),
                        _resolve_format(fmt, lambda at: bytes(text[at:at + (1 << 16)])))
     dev = dev or default_device()
     p = parse(dev, text, fmt, min_qual, phred_offset)
+    if hpc:
+        p = _hpc_parsed(p)
     try:
         r = count_groups(p, k, False, canonical, ordered=False)
         d_h = dev.alloc(8 * nbins)
@@ -2430,6 +2441,99 @@ def emit_reads(p: Parsed, keep, sink, *, span=None, trim=False):
         off = list(p.rec_hdr) + [p.text_bytes]
         return _to(sink, _cut_host(text, off, keep, span, trim))
     return cut_records(p, keep, sink, span=span, trim=trim)
+
+
+# ------------------------------------------------- homopolymer compression
+#
+# One more transformation of the parsed codes, like the -q mask and the mate
+# zip: every run of one base collapses to its first base (kman_hpc_records;
+# the rule: include/kman.h).  Everything downstream takes the new Parsed.
+
+
+def hpc(p: Parsed, *, keep_map: bool = False) -> Parsed:
+    """p with homopolymer-compressed codes (kman_hpc_records): a new Parsed
+    with the kept codes (a record's first base, N and other letters and bases
+    masked by -q are always kept, so the mask is applied before the
+    compression), the new ``rec_seq`` and ``n_bases`` and p's names,
+    ``rec_hdr``, ``text`` and ``text_bytes``, so cut_records still writes the
+    original records.  `keep_map`: the result also carries ``hpc_orig`` (the
+    original index of every kept base, u64 on the device), ``hpc_rec_seq`` and
+    ``hpc_n_bases`` (p's own), for hpc_spans.  ``p.codes`` is freed (peak:
+    twice the codes, plus 8 B per base for the map); the result owns the text
+    and every buffer, and p must not be used afterwards."""
+    if p.mates is not None:
+        raise AssertionError("hpc takes a plain parse: compress each input before zip_pairs")
+    dev, R, n = p.dev, int(p.n_records), int(p.n_bases)
+    codes = d_rec = d_out = orig = None
+    try:
+        codes = dev.alloc(n + 64)
+        d_rec, d_out = dev.alloc(max(16, 8 * R)), dev.alloc(max(16, 8 * R))
+        if R:
+            dev.upload(d_rec, np.ascontiguousarray(p.rec_seq, dtype=np.uint64))
+        if keep_map:
+            orig = dev.alloc(max(16, 8 * n))
+        n_out = c_uint64(0)
+        N.check(dev.ctx, N.lib().kman_hpc_records(
+            dev.ctx, c_void_p(p.codes.ptr), n, c_void_p(d_rec.ptr), R, c_void_p(codes.ptr), c_void_p(d_out.ptr),
+            c_void_p(orig.ptr) if orig is not None else None, byref(n_out)), "kman_hpc_records")
+        rec_seq = dev.download(d_out, R, np.uint64) if R else np.zeros(0, np.uint64)
+        res, codes, omap, orig = codes, None, orig, None
+    finally:
+        for b in (codes, d_rec, d_out, orig):
+            if b is not None:
+                b.free()
+    p.codes.free()
+    text, p.text = p.text, None
+    phases.mark("hpc")
+    return Parsed(dev, res, int(n_out.value), R, p.rec_hdr, rec_seq, p.names, p.names_blob, p.name_off, p.n_masked,
+                  text=text, text_bytes=p.text_bytes, hpc_orig=omap,
+                  hpc_rec_seq=np.ascontiguousarray(p.rec_seq, dtype=np.uint64) if keep_map else None,
+                  hpc_n_bases=n if keep_map else 0)
+
+
+_hpc_parsed = hpc  # (for callers whose own `hpc` argument hides the function)
+
+
+def hpc_spans(p: Parsed, span):
+    """(START, END) per record of hpc(keep_map=True)'s result, from compressed
+    columns to the columns of the original record: START_o = orig[rs_c +
+    START] - rs_o, END_o = orig[rs_c + END] - rs_o, or, when END is the
+    compressed record's length, the original record's length: the whole run of
+    the stretch's last base lies inside it.  A record without a stretch (END
+    <= START) gets 0 and 0.  The two look-ups per record are one kman_gather
+    from the device map."""
+    if p.hpc_orig is None:
+        raise AssertionError("hpc_spans needs the map: hpc(p, keep_map=True)")
+    dev, R = p.dev, int(p.n_records)
+    start, end = _span_arrays(span, R)
+    if R == 0:
+        return start, end
+    rs_c = np.ascontiguousarray(p.rec_seq, dtype=np.uint64)
+    rs_o = p.hpc_rec_seq
+    end_c = np.append(rs_c[1:], np.uint64(p.n_bases))
+    end_o = np.append(rs_o[1:], np.uint64(p.hpc_n_bases))
+    has = (end > start) & (rs_c + end <= end_c)
+    inner = has & (rs_c + end < end_c)  # END is a base of the record: its first original column ends the stretch
+    idx = np.zeros(2 * R, dtype=np.uint64)
+    idx[:R] = np.where(has, rs_c + start, np.uint64(0))
+    idx[R:] = np.where(inner, rs_c + end, np.uint64(0))
+    if not has.any():
+        return np.zeros(R, np.uint64), np.zeros(R, np.uint64)
+    d_idx = d_val = None
+    try:
+        d_idx, d_val = dev.alloc(idx.nbytes), dev.alloc(idx.nbytes)
+        dev.upload(d_idx, idx)
+        N.check(dev.ctx, N.lib().kman_gather(dev.ctx, c_void_p(p.hpc_orig.ptr), c_void_p(d_idx.ptr), 2 * R,
+                                             c_void_p(d_val.ptr), 8), "gather")
+        val = dev.download(d_val, 2 * R, np.uint64)
+    finally:
+        for b in (d_idx, d_val):
+            if b is not None:
+                b.free()
+    zero = np.uint64(0)
+    s_o = np.where(has, val[:R] - rs_o, zero).astype(np.uint64)
+    e_o = np.where(has, np.where(inner, val[R:], end_o) - rs_o, zero).astype(np.uint64)
+    return np.ascontiguousarray(s_o), np.ascontiguousarray(e_o)
 
 
 # ------------------------------------------------------------------ read pairs

@@ -330,3 +330,11 @@ def reads_out_prefix():
 
 def re_sort():
     return click.option("--re-sort", "-R", is_flag=True, help="Force batch re-sorting, when loaded with -B.")
+
+
+def hpc():
+    return click.option("--hpc", "hpc", is_flag=True,
+                        help="Homopolymer-compressed k-mers: every run of one base in every input collapses to one "
+                             "base on the GPU before k-mers are taken (minimap2 -H, meryl compress), so a wrong "
+                             "homopolymer length in a long read costs no k-mer; N and other letters are kept, and "
+                             "no run crosses a record")

@@ -37,10 +37,11 @@ def main():
 
 
 def _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist=False, fmt="auto",
-             min_qual=0, phred_offset=33):
+             min_qual=0, phred_offset=33, hpc=False):
+    kw = {"hpc": True} if hpc else {}  # (absent: today's call)
     return (
         FastaBatcher(scan_mode=FastaBatcher.MODE[scan_mode], reverse=reverse, size=batch_size, threads=threads,
-                     tmp=tmp, distributed=dist, fmt=fmt, min_qual=min_qual, phred_offset=phred_offset)
+                     tmp=tmp, distributed=dist, fmt=fmt, min_qual=min_qual, phred_offset=phred_offset, **kw)
         .do(input_path, k, BatcherThreading.FEED_MODE[batch_mode])
         .collection
     )
@@ -78,24 +79,25 @@ INPUT runs on rank 0 alone).
 @args.min_count()
 @args.max_count()
 @args.canonical()
+@args.hpc()
 def count(input_path: str, output_path: str, k: int, reverse: bool = False, scan_mode: str = "KMERS",
           batch_size: int = 1000000, batch_mode: str = "APPEND", previous_batches: Optional[str] = None,
           count_mode: str = "SEQ_COUNT", memory_mode: str = "NORMAL", threads: int = 1,
           tmp: str = tempfile.gettempdir(), re_sort: bool = False, input_format: str = "auto",
           min_qual: int = 0, phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None,
-          canonical: bool = False) -> None:
+          canonical: bool = False, hpc: bool = False) -> None:
     input_file_exists(input_path)
     _check_min_qual(min_qual, input_path, input_format, previous_batches)
-    _check_count_options(min_count, max_count, canonical, count_mode, reverse, previous_batches)
+    _check_count_options(min_count, max_count, canonical, count_mode, reverse, previous_batches, hpc=hpc)
     set_tempdir(tmp)
-    dist = _multi_gpu(k, previous_batches, count_mode, input_path, input_format, canonical=canonical)
+    dist = _multi_gpu(k, previous_batches, count_mode, input_path, input_format, canonical=canonical, hpc=hpc)
     if dist is None:
         return  # (a rank other than 0, for work outside the multi-GPU domain)
     if previous_batches is not None:
         batches = load_batches(previous_batches, threads, re_sort)
     else:
         batches = _batches(input_path, k, reverse, scan_mode, batch_size, batch_mode, threads, tmp, dist,
-                           input_format, min_qual, int(phred_offset))
+                           input_format, min_qual, int(phred_offset), hpc)
     joiner = prep_joiner(KJoinerThreading(KJoiner.MODE[count_mode], KJoiner.MEMORY[memory_mode]), len(batches),
                          threads)
     joiner.min_count, joiner.max_count, joiner.canonical = min_count, max_count, canonical
@@ -104,9 +106,10 @@ def count(input_path: str, output_path: str, k: int, reverse: bool = False, scan
 
 
 def _check_count_options(min_count: int, max_count: Optional[int], canonical: bool, count_mode: str, reverse: bool,
-                         previous_batches: Optional[str]) -> None:
-    """The abundance range and --canonical of `kmer count`: what they cannot
-    be combined with is refused before any device work or output."""
+                         previous_batches: Optional[str], *, hpc: bool = False) -> None:
+    """The abundance range, --canonical and --hpc of `kmer count`: what they
+    cannot be combined with is refused before any device work or output.
+    --hpc follows --canonical's restrictions."""
     filtered = min_count > 1 or max_count is not None
     if max_count is not None and min_count > max_count:
         raise AssertionError("--min-count %d is greater than --max-count %d" % (min_count, max_count))
@@ -116,6 +119,28 @@ def _check_count_options(min_count: int, max_count: Optional[int], canonical: bo
         raise AssertionError("--canonical with -r: the strands are already folded into one k-mer")
     if canonical and previous_batches is not None:
         raise AssertionError("--canonical with -B: canonical k-mers come from the INPUT, not from reloaded batches")
+    if hpc and count_mode != "SEQ_COUNT":
+        raise AssertionError("--hpc needs -m SEQ_COUNT, not %s" % count_mode)
+    if hpc and reverse:
+        raise AssertionError("--hpc with -r: as --canonical, it counts one strand's stream of the INPUT")
+    if hpc and previous_batches is not None:
+        raise AssertionError("--hpc with -B: the compressed k-mers come from the INPUT, not from reloaded batches")
+
+
+def _parse_input(dev, path: str, input_format: str, min_qual: int, phred_offset: int, hpc: bool = False, *,
+                 keep_text: bool = False, keep_map: bool = False):
+    """engine.parse_file, and under --hpc the compression right after it."""
+    if keep_text:
+        p = engine.parse_file(dev, path, input_format, min_qual, phred_offset, keep_text=True)
+    else:  # (not one allocation or call differs from a run without the options)
+        p = engine.parse_file(dev, path, input_format, min_qual, phred_offset)
+    if not hpc:
+        return p
+    try:
+        return engine.hpc(p, keep_map=keep_map)
+    except BaseException:
+        p.free()
+        raise
 
 
 def _check_min_qual(min_qual: int, input_path: str, input_format: str,
@@ -135,16 +160,19 @@ def _is_fastq(input_path: Optional[str], input_format: str) -> bool:
 
 def _multi_gpu(k: int, previous_batches: Optional[str], count_mode: str = "SEQ_COUNT",
                input_path: Optional[str] = None, input_format: str = "auto", *,
-               canonical: bool = False) -> Optional[bool]:
+               canonical: bool = False, hpc: bool = False) -> Optional[bool]:
     """Under a one-process-per-GPU launch (kman_amd/launch.py): True = this
     rank joins across the GPUs; False = the single-GPU path (no launch, or
     rank 0 alone for work outside the multi-GPU domain: k > 32, -B reloads,
-    VEC_* modes, fastq input, count --canonical); None = a rank that leaves
+    VEC_* modes, fastq input, count --canonical or --hpc); None = a rank that leaves
     that work to rank 0."""
     if not launch.distributed():
         return False
     if canonical and k > 1:
         launch.log_solo("count --canonical")  # (ordered canonical rows across ranks: DESIGN §8)
+        return False if launch.solo_rank() else None
+    if hpc and k > 1:
+        launch.log_solo("count --hpc")  # (a run may cross a shard's cut: DESIGN §8)
         return False if launch.solo_rank() else None
     if k > 1 and previous_batches is None and _is_fastq(input_path, input_format):
         launch.log_solo("fastq input")  # (the byte-range shards cut FASTA only)
@@ -264,8 +292,9 @@ INPUT fasta or fastq file, plain or gzipped.
 @args.input_format()
 @args.min_qual()
 @args.phred_offset()
+@args.hpc()
 def hist(input_path: str, output_path: str, k: int, forward: bool = False, max_count: int = 10000,
-         input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33") -> None:
+         input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33", hpc: bool = False) -> None:
     input_file_exists(input_path)
     _check_min_qual(min_qual, input_path, input_format)
     if k <= 1:
@@ -277,7 +306,10 @@ def hist(input_path: str, output_path: str, k: int, forward: bool = False, max_c
     if launch.distributed() and k > engine.MAX_K and not launch.solo_rank():
         launch.log_solo("kmer hist k=%d" % k)
         return
-    if launch.distributed() and k <= engine.MAX_K and not fastq:
+    if launch.distributed() and hpc and not launch.solo_rank():
+        launch.log_solo("kmer hist --hpc")  # (a run may cross a shard's cut)
+        return
+    if launch.distributed() and k <= engine.MAX_K and not fastq and not hpc:
         # every rank counts its shard's (canonical) k-mers, the spectrum is
         # all-reduced, rank 0 writes it
         src = launch.ShardedSource(engine.default_device(), input_path, k, False)
@@ -290,8 +322,9 @@ def hist(input_path: str, output_path: str, k: int, forward: bool = False, max_c
                 fh.write(engine.format_hist(h))
         logging.info("That's all!")
         return
+    kw = {"hpc": True} if hpc else {}  # (absent: today's call)
     h = engine.abundance_hist(engine.read_input(input_path), k, canonical=not forward, nbins=max_count + 1,
-                              fmt=input_format, min_qual=min_qual, phred_offset=int(phred_offset))
+                              fmt=input_format, min_qual=min_qual, phred_offset=int(phred_offset), **kw)
     with open(output_path, "wb") as fh:
         fh.write(engine.format_hist(h))
     logging.info("That's all!")
@@ -322,9 +355,10 @@ Launched one process per GPU, the command runs on rank 0 alone.
 @args.phred_offset()
 @args.min_count()
 @args.max_count()
+@args.hpc()
 def sets(input_a: str, input_b: str, output_path: str, k: int, op: str, counts: Optional[str] = None,
          reverse: bool = False, canonical: bool = False, input_format: str = "auto", min_qual: int = 0,
-         phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None) -> None:
+         phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None, hpc: bool = False) -> None:
     input_file_exists(input_a)
     input_file_exists(input_b)
     fastq = [_is_fastq(p, input_format) for p in (input_a, input_b)]
@@ -337,7 +371,7 @@ def sets(input_a: str, input_b: str, output_path: str, k: int, op: str, counts: 
     try:
         for path, fq in zip((input_a, input_b), fastq):
             # (A's parse buffers are freed before B is read)
-            p = engine.parse_file(dev, path, input_format, min_qual if fq else 0, int(phred_offset))
+            p = _parse_input(dev, path, input_format, min_qual if fq else 0, int(phred_offset), hpc)
             try:
                 engine.check_empty_names(p, k)
                 r = engine.join_groups(p, k, reverse, "count", canonical=canonical)
@@ -458,6 +492,7 @@ Launched one process per GPU, the command runs on rank 0 alone.
 @args.interleaved()
 @args.reads_out2()
 @args.index_bits()
+@args.hpc()
 def screen(reads_path: str, table_input: str, output_path: str, k: int, canonical: bool = False,
            input_format: str = "auto", min_qual: int = 0, phred_offset: str = "33", min_count: int = 1,
            max_count: Optional[int] = None, min_hits: int = 0, min_frac: float = 0.0, invert: bool = False,
@@ -465,7 +500,7 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
            max_median: Optional[int] = None, solid: Optional[int] = None, min_solid_len: Optional[int] = None,
            bed_path: Optional[str] = None, reads_out: Optional[str] = None, trim: bool = False,
            correct: bool = False, mate_path: Optional[str] = None, interleaved: bool = False,
-           reads_out2: Optional[str] = None) -> None:
+           reads_out2: Optional[str] = None, hpc: bool = False) -> None:
     input_file_exists(reads_path)
     input_file_exists(table_input)
     fastq = [_is_fastq(p, input_format) for p in (reads_path, table_input)]
@@ -476,7 +511,7 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
     _check_screen_options(k, min_qual, fastq, min_count, max_count, min_hits, min_frac, index_bits, min_median,
                           max_median, solid, min_solid_len, bed_path, reads_out=reads_out, trim=trim,
                           output_path=output_path, correct=correct, mate_path=mate_path, interleaved=interleaved,
-                          reads_out2=reads_out2, fastq_mate=fastq_mate)
+                          reads_out2=reads_out2, fastq_mate=fastq_mate, hpc=hpc)
     median = median or min_median is not None or max_median is not None
     if launch.distributed() and not launch.solo_rank():
         launch.log_solo("kmer screen")  # (the table and the reads on one GPU: DESIGN §8)
@@ -485,7 +520,7 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
     table = None
     try:
         # (the table input's parse buffers are freed before READS is parsed)
-        p = engine.parse_file(dev, table_input, input_format, min_qual if fastq[1] else 0, int(phred_offset))
+        p = _parse_input(dev, table_input, input_format, min_qual if fastq[1] else 0, int(phred_offset), hpc)
         try:
             engine.check_empty_names(p, k)
             table = engine.join_groups(p, k, False, "count", canonical=canonical)
@@ -500,14 +535,11 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
         if mate_path is not None or interleaved:
             _screen_pairs(dev, table, reads_path, mate_path, output_path, canonical, input_format,
                           min_qual if fastq[0] else 0, int(phred_offset), min_hits, min_frac, invert, index_bits,
-                          median, min_median, max_median, solid, min_solid_len, reads_out, reads_out2, trim)
+                          median, min_median, max_median, solid, min_solid_len, reads_out, reads_out2, trim, hpc)
             logging.info("That's all!")
             return
-        if reads_out is None:  # (not one allocation or call differs from a run without the option)
-            p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset))
-        else:
-            p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset),
-                                  keep_text=True)
+        p = _parse_input(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset), hpc,
+                         keep_text=reads_out is not None, keep_map=hpc and solid is not None)
         try:
             span = fixes = None
             if correct:  # (then every step below reads the corrected codes, and --reads-out the corrected text)
@@ -516,6 +548,8 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
                 stats, med, runs = engine.screen_solid(p, table, canonical, solid, median=median,
                                                        index_bits=index_bits)
                 span = engine.solid_spans(runs, k)
+                if hpc:  # (START, END, --min-solid-len, --bed and --trim: the original record's columns)
+                    span = engine.hpc_spans(p, span)
                 keep = engine.screen_keep(stats, min_hits, min_frac, invert, median=med, min_median=min_median,
                                           max_median=max_median, span=span, min_solid_len=min_solid_len)
             elif median:
@@ -544,11 +578,15 @@ def screen(reads_path: str, table_input: str, output_path: str, k: int, canonica
 
 
 def _parse_pairs(dev, reads_path: str, mate_path: Optional[str], input_format: str, min_qual: int,
-                 phred_offset: int, keep_text: bool):
+                 phred_offset: int, keep_text: bool, hpc: bool = False):
     """(mate view, pair view) of READS and READS2 (zipped on the GPU), or of an
     interleaved READS alone (`mate_path` None).  Freeing the mate view frees
-    everything; the pair view borrows its codes."""
-    p1 = engine.parse_file(dev, reads_path, input_format, min_qual, phred_offset, keep_text=keep_text)
+    everything; the pair view borrows its codes.  `hpc`: every input is
+    compressed right after its parse, before the zip."""
+    def parse(path):
+        return _parse_input(dev, path, input_format, min_qual, phred_offset, hpc, keep_text=keep_text)
+
+    p1 = parse(reads_path)
     if mate_path is None:
         try:
             return p1, engine.pairs_of(p1)
@@ -557,7 +595,7 @@ def _parse_pairs(dev, reads_path: str, mate_path: Optional[str], input_format: s
             raise
     p2 = None
     try:
-        p2 = engine.parse_file(dev, mate_path, input_format, min_qual, phred_offset, keep_text=keep_text)
+        p2 = parse(mate_path)
         pm = engine.zip_pairs(p1, p2)
     except BaseException:
         p1.free()
@@ -571,10 +609,11 @@ def _screen_pairs(dev, table, reads_path: str, mate_path: Optional[str], output_
                   input_format: str, min_qual: int, phred_offset: int, min_hits: int, min_frac: float, invert: bool,
                   index_bits: Optional[int], median: bool, min_median: Optional[int], max_median: Optional[int],
                   solid: Optional[int], min_solid_len: Optional[int], reads_out: Optional[str],
-                  reads_out2: Optional[str], trim: bool) -> None:
+                  reads_out2: Optional[str], trim: bool, hpc: bool = False) -> None:
     """`kmer screen --mate` / `--interleaved`: one line per pair, the listed
     pairs' records in step."""
-    pm, pv = _parse_pairs(dev, reads_path, mate_path, input_format, min_qual, phred_offset, reads_out is not None)
+    pm, pv = _parse_pairs(dev, reads_path, mate_path, input_format, min_qual, phred_offset, reads_out is not None,
+                          hpc)
     try:
         stats, med, runs = engine.screen_pairs(pm, pv, table, canonical, median=median, min_count=solid,
                                                index_bits=index_bits)
@@ -601,8 +640,15 @@ def _check_screen_options(k: int, min_qual: int, fastq, min_count: int, max_coun
                           reads_out: Optional[str] = None, trim: bool = False,
                           output_path: Optional[str] = None, correct: bool = False,
                           mate_path: Optional[str] = None, interleaved: bool = False,
-                          reads_out2: Optional[str] = None, fastq_mate: Optional[bool] = None) -> None:
+                          reads_out2: Optional[str] = None, fastq_mate: Optional[bool] = None,
+                          hpc: bool = False) -> None:
     """What `kmer screen` refuses, before any device work or output."""
+    if hpc and correct:
+        raise AssertionError("--hpc with --correct: a substitution changes the runs, so the compressed reads "
+                             "cannot be repaired in place")
+    if hpc and solid is not None and (mate_path is not None or interleaved):
+        raise AssertionError("--hpc with --solid is not offered for read pairs: the map to original columns is "
+                             "not zipped")
     if mate_path is not None and interleaved:
         raise AssertionError("--mate and --interleaved exclude each other: the pairs are in two files or in one")
     if reads_out2 is not None and mate_path is None:
@@ -739,11 +785,13 @@ Launched one process per GPU, the command runs on rank 0 alone.
 @args.mate()
 @args.interleaved()
 @args.index_bits()
+@args.hpc()
 def classify(reads_path: str, output_path: str, k: int, refs=(), canonical: bool = False, input_format: str = "auto",
              min_qual: int = 0, phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None,
              specific: bool = False, min_hits: int = 1, min_frac: float = 0.0, min_margin: int = 1,
              hits: bool = False, summary_path: Optional[str] = None, reads_out_prefix: Optional[str] = None,
-             index_bits: Optional[int] = None, mate_path: Optional[str] = None, interleaved: bool = False) -> None:
+             index_bits: Optional[int] = None, mate_path: Optional[str] = None, interleaved: bool = False,
+             hpc: bool = False) -> None:
     input_file_exists(reads_path)
     refs = list(refs)
     for path in refs:
@@ -770,7 +818,7 @@ def classify(reads_path: str, output_path: str, k: int, refs=(), canonical: bool
     try:
         for path, fq in zip(refs, fastq[1:]):
             # (a reference's parse buffers are freed before the next one is read)
-            p = engine.parse_file(dev, path, input_format, min_qual if fq else 0, int(phred_offset))
+            p = _parse_input(dev, path, input_format, min_qual if fq else 0, int(phred_offset), hpc)
             try:
                 engine.check_empty_names(p, k)
                 t = engine.join_groups(p, k, False, "count", canonical=canonical)
@@ -790,11 +838,11 @@ def classify(reads_path: str, output_path: str, k: int, refs=(), canonical: bool
             if paired:
                 _classify_pairs(dev, ctable, nc, index, reads_path, mate_path, output_path, canonical, specific,
                                 input_format, min_qual if fastq[0] else 0, int(phred_offset), min_hits, min_frac,
-                                min_margin, hits, summary_path, labels, table_kmers, pair_outs, index_bits)
+                                min_margin, hits, summary_path, labels, table_kmers, pair_outs, index_bits, hpc)
                 logging.info("That's all!")
                 return
-            p = engine.parse_file(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset),
-                                  keep_text=reads_out_prefix is not None)
+            p = _parse_input(dev, reads_path, input_format, min_qual if fastq[0] else 0, int(phred_offset), hpc,
+                             keep_text=reads_out_prefix is not None)
             try:
                 res = engine.classify(p, ctable, nc, canonical, specific, index=index, index_bits=index_bits,
                                       planes=hits)
@@ -823,10 +871,10 @@ def classify(reads_path: str, output_path: str, k: int, refs=(), canonical: bool
 def _classify_pairs(dev, ctable, nc: int, index, reads_path: str, mate_path: Optional[str], output_path: str,
                     canonical: bool, specific: bool, input_format: str, min_qual: int, phred_offset: int,
                     min_hits: int, min_frac: float, min_margin: int, hits: bool, summary_path: Optional[str], labels,
-                    table_kmers, pair_outs, index_bits: Optional[int]) -> None:
+                    table_kmers, pair_outs, index_bits: Optional[int], hpc: bool = False) -> None:
     """`kmer classify --mate` / `--interleaved`: one label and one line per
     pair, the classes' records in step."""
-    pm, pv = _parse_pairs(dev, reads_path, mate_path, input_format, min_qual, phred_offset, bool(pair_outs))
+    pm, pv = _parse_pairs(dev, reads_path, mate_path, input_format, min_qual, phred_offset, bool(pair_outs), hpc)
     try:
         res = engine.classify(pv, ctable, nc, canonical, specific, index=index, index_bits=index_bits, planes=hits)
         windows, best, nhits, second = res[:4]

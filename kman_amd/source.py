@@ -26,15 +26,18 @@ from . import engine, phases
 
 class FastaSource:
     def __init__(self, dev: engine.Device, text: Optional[bytes], k: int, rc: bool, path: Optional[str] = None,
-                 fmt: str = "auto", min_qual: int = 0, phred_offset: int = 33):
+                 fmt: str = "auto", min_qual: int = 0, phred_offset: int = 33, hpc: bool = False):
         """The k-mer stream of FASTA or FASTQ bytes (`text`), or of the file at
         `path` (engine.parse_file: chunked pinned reads overlapping the H2D);
         `fmt`: "auto" (engine.sniff_format), "fasta" or "fastq"; `min_qual`,
-        `phred_offset`: engine.parse_fastq's quality threshold."""
+        `phred_offset`: engine.parse_fastq's quality threshold; `hpc`: the
+        codes are homopolymer-compressed right after the parse (engine.hpc)."""
         engine._check_k(k, wide=True)
         self.dev, self.k, self.rc = dev, k, rc
         self.parsed = (engine.parse_file(dev, path, fmt, min_qual, phred_offset) if text is None
                        else engine.parse(dev, text, fmt, min_qual, phred_offset))
+        if hpc:
+            self.parsed = engine.hpc(self.parsed)
         engine.check_empty_names(self.parsed, k)
         self.n_kmers = engine.count_kmers(self.parsed, k, rc)
         self._km = {}  # want_pos -> engine.Kmers (stream order)
