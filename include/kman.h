@@ -745,6 +745,49 @@ int kman_classify_records(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_base
 int kman_classify_pick(kman_ctx *ctx, const uint32_t *d_planes, uint64_t n_records, uint32_t n_colors,
                        uint32_t *d_pick);
 
+/* ------------------------------------------- all pairs of a coloured table
+ * Not in the reference: how many rows of a coloured table every two of its
+ * colours share, the Gram matrix of the bit matrix whose rows are the masks
+ * (`kmer compare`: Jaccard, containment and Mash distance of up to 64 inputs
+ * from one pass over the table).
+ *
+ * kman_mask_gram: d_masks, n u64 masks (a coloured table's counts), 8-byte
+ *   aligned and no stricter, never written.  Bits at or above n_colors are
+ *   ignored: m' = m & (2^n_colors - 1), all 64 bits when n_colors == 64.
+ *     d_gram     n_colors x n_colors u64, row-major: G[i][j] = the rows with
+ *                bits i and j of m' both set.  Symmetric, both triangles
+ *                written; G[c][c] is the row count of colour c.
+ *     d_occ      n_colors + 1 u64, may be NULL: occ[p] = the rows with
+ *                popcount(m') == p (occ[0]: rows of none of the colours).
+ *     d_private  n_colors u64, may be NULL: private[c] = the rows with
+ *                m' == 1 << c.
+ *   Every non-NULL output is zeroed by the call itself, then filled.  n == 0:
+ *   the outputs are zeroed, d_masks is not read and nothing is launched.
+ *   n_colors outside 1..KMAN_CLASSIFY_MAX_COLORS, a NULL d_gram, or
+ *   n > KMAN_GRAM_MAX_ROWS: KMAN_EINVAL.  A refused call writes nothing.
+ *   The work per row does not depend on how many bits the row has set: a wave
+ *   takes 64 masks per step (lanes past n contribute 0), forms the n_colors
+ *   column words with one 64-lane ballot per colour, lane c keeping column c
+ *   and parking it in the wave's own LDS slice; lane i then adds
+ *   popcount(col_i AND col_(i+d) mod n_colors) for d = 0 .. n_colors / 2 (every
+ *   unordered pair once, at most 33 rounds for the 2080 pairs of 64 colours)
+ *   into registers across a grid-stride loop.  occ comes from the ballots of
+ *   the seven bits of popcount(m'), private from col_c AND
+ *   ballot(popcount(m') == 1).  The accumulators are 32-bit: a step adds at
+ *   most 64 and a wave runs at most KMAN_GRAM_MAX_ROWS / (KMAN_GRAM_MAX_BLOCKS *
+ *   KMAN_GRAM_THREADS) = 2^22 steps, so a block's sums stay below 2^30.  They
+ *   are added up in LDS and flushed ONCE per block, one 64-bit integer atomic
+ *   per nonzero entry (two for i != j): two identical calls give identical
+ *   bytes.  Grid: min(KMAN_GRAM_MAX_BLOCKS, ceil(n / KMAN_GRAM_THREADS)) blocks
+ *   of KMAN_GRAM_THREADS threads (four per CU on 256 CUs), not proportional to
+ *   n; one grid stride is KMAN_GRAM_MAX_BLOCKS * KMAN_GRAM_THREADS rows.
+ *   Launches are timed under the tag "gram".  Synchronises. */
+#define KMAN_GRAM_THREADS 256
+#define KMAN_GRAM_MAX_BLOCKS 1024
+#define KMAN_GRAM_MAX_ROWS (1ull << 40)
+int kman_mask_gram(kman_ctx *ctx, const uint64_t *d_masks, uint64_t n, uint32_t n_colors, uint64_t *d_gram,
+                   uint64_t *d_occ, uint64_t *d_private);
+
 /* ------------------------------------------- per-record order statistic
  * Not in the reference: one quantile (the median, by default) of the table
  * counts of a record's k-mer windows.  A sum commutes and an order statistic

@@ -63,6 +63,9 @@ KMAN_CORRECT_REC_CAP = 512  # rec_seq entries of a tile staged in LDS; more: sea
 KMAN_CLASSIFY_MAX_COLORS = 64  # references of one coloured table: a row's mask is one u64 (include/kman.h)
 KMAN_CLASSIFY_SPECIFIC = 16  # kman_classify_records: count a window only for the one reference that holds it
 KMAN_CLASSIFY_NONE = 0xFFFFFFFF  # kman_classify_pick: no colour has a hit
+KMAN_GRAM_THREADS = 256  # threads per block of kman_mask_gram (include/kman.h)
+KMAN_GRAM_MAX_BLOCKS = 1024  # its largest grid: one grid stride is KMAN_GRAM_MAX_BLOCKS * KMAN_GRAM_THREADS rows
+KMAN_GRAM_MAX_ROWS = 1 << 40  # more rows are refused (the kernel's 32-bit accumulators)
 KMAN_MATCH_RIGHT = 0
 KMAN_MATCH_LEFT = 1
 KMAN_MATCH_MIN = 2
@@ -246,6 +249,7 @@ SIGNATURES = {
                 c_void_p, c_uint32, c_uint32, c_void_p],
     ),
     "kman_classify_pick": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p]),
+    "kman_mask_gram": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]),
     "kman_format_classify": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_char_p, c_void_p,
                 c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t), c_int],

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import ctypes
 import logging
+import math
 import os
 from collections.abc import Sequence as _SequenceABC
 from ctypes import byref, c_int, c_size_t, c_uint32, c_uint64, c_void_p
@@ -2995,6 +2996,141 @@ def emit_classify(p: Parsed, labels, windows, assign, hits, second, sink=None, *
     return _to(sink, _format(N.lib().kman_format_classify, w.ctypes.data_as(c_void_p), a.ctypes.data_as(c_void_p),
                              h.ctypes.data_as(c_void_p), s.ctypes.data_as(c_void_p), pp, nc, R, kp, blob,
                              loff.ctypes.data_as(c_void_p), p.names_blob, off.ctypes.data_as(c_void_p)))
+
+
+# ------------------------------------------------- all pairs of a coloured table (compare)
+
+COMPARE_METRICS = ("jaccard", "dist", "shared", "containment")
+
+
+def mask_gram(dev: Device, ctable: CountResult, n_colors: int):
+    """kman_mask_gram on a coloured table (color_table): (gram, occ, private),
+    numpy u64 arrays of shapes (n_colors, n_colors), (n_colors + 1,) and
+    (n_colors,).  gram[i][j]: the rows held by references i and j (the
+    diagonal: each reference's rows); occ[p]: the rows held by exactly p
+    references; private[c]: the rows held by reference c alone.  An empty
+    table gives zeros."""
+    if isinstance(n_colors, bool) or not isinstance(n_colors, (int, np.integer)) or not 1 <= n_colors <= MAX_COLORS:
+        raise AssertionError("n_colors must be an integer in [1, %d], got %r" % (MAX_COLORS, n_colors))
+    if ctable.count_bytes != 8:
+        raise AssertionError("mask_gram takes a coloured table (8-byte masks: color_table), got %d-byte counts"
+                             % ctable.count_bytes)
+    nc, n = int(n_colors), int(ctable.n)
+    words = nc * nc + (nc + 1) + nc
+    d_out = dev.alloc(8 * words)
+    try:
+        N.check(dev.ctx, N.lib().kman_mask_gram(
+            dev.ctx, c_void_p(ctable.counts.ptr if n else None), n, nc, c_void_p(d_out.ptr),
+            c_void_p(d_out.ptr + 8 * nc * nc), c_void_p(d_out.ptr + 8 * (nc * nc + nc + 1))), "kman_mask_gram")
+        out = dev.download(d_out, words, np.uint64)
+    finally:
+        d_out.free()
+    return out[:nc * nc].reshape(nc, nc).copy(), out[nc * nc:nc * nc + nc + 1].copy(), out[nc * nc + nc + 1:].copy()
+
+
+def compare_rows(gram, k: int):
+    """The per-pair metrics of mask_gram's matrix, computed in float64 from
+    the exact integers: a list of (i, j, a, b, s, jaccard, cont_i, cont_j,
+    dist) for every pair i < j, a = gram[i][i], b = gram[j][j], s =
+    gram[i][j] as Python ints.  See compare_metrics."""
+    g = np.asarray(gram, dtype=np.uint64)
+    if g.ndim != 2 or g.shape[0] != g.shape[1]:
+        raise AssertionError("compare_rows takes a square matrix, got %r" % (g.shape,))
+    rows = []
+    for i in range(g.shape[0]):
+        for j in range(i + 1, g.shape[0]):
+            a, b, s = int(g[i, i]), int(g[j, j]), int(g[i, j])
+            rows.append((i, j, a, b, s) + compare_metrics(a, b, s, k))
+    return rows
+
+
+def compare_metrics(a: int, b: int, s: int, k: int):
+    """(jaccard, containment of the first, containment of the second, Mash
+    distance) of two k-mer sets of a and b k-mers that share s, with u = a +
+    b - s: J = s / u (0 when u == 0); s / a and s / b (0 for an empty set);
+    D = -ln(2 J / (1 + J)) / k, 1 when J == 0, exactly 0 when J == 1, clamped
+    to [0, 1]."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise AssertionError("k must be a positive integer, got %r" % (k,))
+    a, b, s = int(a), int(b), int(s)
+    u = a + b - s
+    jac = float(s) / float(u) if u else 0.0
+    ca = float(s) / float(a) if a else 0.0
+    cb = float(s) / float(b) if b else 0.0
+    if jac <= 0.0:
+        dist = 1.0
+    elif jac >= 1.0:
+        dist = 0.0
+    else:
+        dist = min(1.0, max(0.0, -math.log(2.0 * jac / (1.0 + jac)) / float(k)))
+    return jac, ca, cb, dist
+
+
+def _compare_labels(labels, n: int):
+    labels = [x.decode("utf-8", errors="surrogateescape") if isinstance(x, bytes) else str(x) for x in labels]
+    if len(labels) != n:
+        raise AssertionError("%d labels for %d inputs" % (len(labels), n))
+    return labels
+
+
+def emit_compare(labels, gram, k: int, sink=None):
+    """The `kmer compare` text: one "LABEL_I<TAB>LABEL_J<TAB>KMERS_I<TAB>
+    KMERS_J<TAB>SHARED<TAB>JACCARD<TAB>CONT_I<TAB>CONT_J<TAB>DIST" line per
+    pair i < j in input order, the reals as %.6f.  Plain host formatting.
+    Returned, or written to the binary file `sink`."""
+    g = np.asarray(gram, dtype=np.uint64)
+    labels = _compare_labels(labels, g.shape[0])
+    out = ["%s\t%s\t%d\t%d\t%d\t%.6f\t%.6f\t%.6f\t%.6f\n" % ((labels[i], labels[j]) + tuple(r))
+           for (i, j, *r) in compare_rows(g, k)]
+    return _to(sink, "".join(out).encode("utf-8", errors="surrogateescape"))
+
+
+def emit_compare_matrix(labels, gram, k: int, metric: str = "dist", sink=None):
+    """The `kmer compare --matrix` text: a first line with the number of
+    inputs, then "LABEL<TAB>v_0<TAB>...<TAB>v_{n-1}" per input.  metric:
+    "dist", "jaccard", "containment" (row in column, gram[r][c] / gram[r][r]:
+    not symmetric) as %.6f, or "shared" as integers.  The diagonal is the
+    input's k-mers (shared), 1 (jaccard, containment; 0 for an empty input)
+    and 0 (dist)."""
+    if metric not in COMPARE_METRICS:
+        raise AssertionError("metric must be one of %s, got %r" % (", ".join(COMPARE_METRICS), metric))
+    g = np.asarray(gram, dtype=np.uint64)
+    n = g.shape[0]
+    labels = _compare_labels(labels, n)
+    out = ["%d\n" % n]
+    for r in range(n):
+        cells = []
+        for c in range(n):
+            a, b, s = int(g[r, r]), int(g[c, c]), int(g[r, c])
+            if metric == "shared":
+                cells.append("%d" % s)
+                continue
+            jac, ca, _, dist = compare_metrics(a, b, s, k)
+            if r == c:
+                jac, ca, dist = (1.0 if a else 0.0), (1.0 if a else 0.0), 0.0
+            cells.append("%.6f" % {"jaccard": jac, "containment": ca, "dist": dist}[metric])
+        out.append("\t".join([labels[r]] + cells) + "\n")
+    return _to(sink, "".join(out).encode("utf-8", errors="surrogateescape"))
+
+
+def emit_occupancy(occ, sink=None):
+    """The `kmer compare --occupancy` text, the pan-genome spectrum: "P<TAB>
+    KMERS" for P = 1 .. n, the k-mers held by exactly P inputs (P = n: the
+    core).  `occ`: mask_gram's second array (occ[0] is not written)."""
+    o = np.asarray(occ, dtype=np.uint64).reshape(-1)
+    return _to(sink, "".join("%d\t%d\n" % (p, int(o[p])) for p in range(1, len(o))).encode())
+
+
+def emit_compare_summary(labels, gram, private, sink=None):
+    """The `kmer compare --summary` text: "LABEL<TAB>KMERS<TAB>PRIVATE" per
+    input (its k-mers, and those of them no other input holds)."""
+    g = np.asarray(gram, dtype=np.uint64)
+    pr = np.asarray(private, dtype=np.uint64).reshape(-1)
+    labels = _compare_labels(labels, g.shape[0])
+    if len(pr) != len(labels):
+        raise AssertionError("%d private counts for %d inputs" % (len(pr), len(labels)))
+    out = ["%s\t%d\t%d\n" % (lab, int(g[c, c]), int(pr[c])) for c, lab in enumerate(labels)]
+    return _to(sink, "".join(out).encode("utf-8", errors="surrogateescape"))
 
 
 def join_groups(p: Parsed, k: int, rc: bool, mode: str, max_keys: Optional[int] = None, canonical: bool = False):

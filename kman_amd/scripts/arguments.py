@@ -338,3 +338,52 @@ def hpc():
                              "base on the GPU before k-mers are taken (minimap2 -H, meryl compress), so a wrong "
                              "homopolymer length in a long read costs no k-mer; N and other letters are kept, and "
                              "no run crosses a record")
+
+
+def compare_inputs():
+    return click.argument("inputs", metavar="INPUT INPUT [INPUT ...]", nargs=-1,
+                          type=click.Path(exists=True, file_okay=True, dir_okay=False, readable=True))
+
+
+def compare_canonical():
+    return click.option("--canonical", "canonical", is_flag=True,
+                        help="Canonical k-mers, min(k-mer, reverse complement), in every input")
+
+
+def compare_min_count():
+    return click.option("--min-count", "-L", "min_count", type=click.IntRange(min=1), default=1,
+                        help="Compare only k-mers seen at least this often in their own input. Default: 1 (all)")
+
+
+def compare_max_count():
+    return click.option("--max-count", "-U", "max_count", type=click.IntRange(min=1), default=None,
+                        help="Compare only k-mers seen at most this often in their own input. Default: no limit")
+
+
+def matrix():
+    return click.option("--matrix", "matrix_path", type=click.Path(dir_okay=False, writable=True), default=None,
+                        metavar="FILE",
+                        help="Also write a square matrix to FILE: a first line with the number of inputs, then "
+                             "LABEL<TAB>v_0<TAB>...<TAB>v_{n-1} per input, the values chosen by --metric")
+
+
+def metric():
+    return click.option("--metric", "metric", type=click.Choice(["jaccard", "dist", "shared", "containment"],
+                                                                case_sensitive=True),
+                        default=None,
+                        help="The values of --matrix: dist (Mash distance, the default), jaccard, shared (integers) "
+                             "or containment (the row's k-mers found in the column, not symmetric). Needs --matrix")
+
+
+def occupancy():
+    return click.option("--occupancy", "occupancy_path", type=click.Path(dir_okay=False, writable=True),
+                        default=None, metavar="FILE",
+                        help="Also write P<TAB>KMERS for P = 1..n to FILE: the k-mers held by exactly P inputs "
+                             "(P = n: the core; P = 1: k-mers of one input only)")
+
+
+def compare_summary():
+    return click.option("--summary", "summary_path", type=click.Path(dir_okay=False, writable=True), default=None,
+                        metavar="FILE",
+                        help="Also write LABEL<TAB>KMERS<TAB>PRIVATE per input to FILE (its k-mers, and those no "
+                             "other input holds)")

@@ -2,7 +2,8 @@
 
 Same arguments, flags, defaults, outputs and errors as the reference CLI; the
 work runs on the GPU through kman_amd (FastaBatcher.do + KJoiner.join).
-``hist``, ``sets``, ``screen`` and ``classify`` are this engine's own commands.
+``hist``, ``sets``, ``screen``, ``classify`` and ``compare`` are this engine's
+own commands.
 """
 
 from __future__ import annotations
@@ -986,6 +987,133 @@ def _check_classify_options(k: int, labels, min_qual: int, fastq, min_count: int
     named = [("OUTPUT", output_path)] + ([("--summary", summary_path)] if summary_path is not None else []) + \
         [("--reads-out-prefix", path) for _, path in outs]
     for i, (na, pa) in enumerate(named):
+        for nb, pb in named[:i]:
+            if _same_path(pa, pb):
+                raise AssertionError("%s and %s name the same file, %r" % (nb, na, pa))
+
+
+@main.command(name="compare", context_settings=CONTEXT_SETTINGS, help="""
+All against all: how many k-mers every two of the INPUT files share, written
+to OUTPUT as one "LABEL_I<TAB>LABEL_J<TAB>KMERS_I<TAB>KMERS_J<TAB>SHARED<TAB>
+JACCARD<TAB>CONT_I<TAB>CONT_J<TAB>DIST" line per pair in input order (JACCARD:
+shared / union; CONT_I: shared / KMERS_I; DIST: the Mash distance
+-ln(2 J / (1 + J)) / K, 1 for disjoint inputs), exact, not sketched.
+
+Not part of the reference kman CLI.  Every INPUT is counted on the GPU and the
+tables are united into one coloured table there, as `kmer classify` builds it
+from its --ref files: each k-mer of any input with the set of inputs that hold
+it.  One pass over that table (kman_mask_gram) gives every pair's shared
+k-mers at once; nothing goes through a text file.  INPUT: fasta or fastq
+files, plain or gzipped, each detected on its own; 2 to 64 of them, K <= 32.
+LABEL is the input's label (its file name without a trailing .gz and then one
+extension); labels must differ.  -L / -U select the k-mers of each input, by
+their count in that input (-L 2 drops the k-mers a read set holds once).
+--matrix FILE writes the square matrix of --metric (dist by default) for
+clustering and tree building, --occupancy FILE the pan-genome spectrum (how
+many k-mers exactly P inputs hold; P = n is the core), --summary FILE
+"LABEL<TAB>KMERS<TAB>PRIVATE" per input.
+Out of scope: abundance-weighted measures such as Bray-Curtis (the coloured
+table keeps no counts), K > 32, more than 64 inputs, sketching, and inputs
+whose union of k-mers does not fit one GPU.
+Launched one process per GPU, the command runs on rank 0 alone.
+""")
+@args.output_path(file_okay=True)
+@args.k()
+@args.compare_inputs()
+@args.compare_canonical()
+@args.input_format()
+@args.min_qual()
+@args.phred_offset()
+@args.compare_min_count()
+@args.compare_max_count()
+@args.matrix()
+@args.metric()
+@args.occupancy()
+@args.compare_summary()
+@args.hpc()
+def compare(output_path: str, k: int, inputs=(), canonical: bool = False, input_format: str = "auto",
+            min_qual: int = 0, phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None,
+            matrix_path: Optional[str] = None, metric: Optional[str] = None, occupancy_path: Optional[str] = None,
+            summary_path: Optional[str] = None, hpc: bool = False) -> None:
+    inputs = list(inputs)
+    for path in inputs:
+        input_file_exists(path)
+    fastq = [_is_fastq(p, input_format) for p in inputs]
+    labels = [ref_label(path) for path in inputs]
+    _check_compare_options(k, inputs, labels, min_qual, fastq, min_count, max_count, output_path, matrix_path, metric,
+                           occupancy_path, summary_path)
+    if launch.distributed() and not launch.solo_rank():
+        launch.log_solo("kmer compare")  # (the coloured table on one GPU, as kmer classify)
+        return
+    dev = engine.default_device()
+    nc = len(inputs)
+    tables, ctable = [], None
+    try:
+        for path, fq in zip(inputs, fastq):
+            # (an input's parse buffers are freed before the next one is read)
+            p = _parse_input(dev, path, input_format, min_qual if fq else 0, int(phred_offset), hpc)
+            try:
+                engine.check_empty_names(p, k)
+                t = engine.join_groups(p, k, False, "count", canonical=canonical)
+            finally:
+                p.free()
+            if t is None:
+                t = engine.empty_count(dev, k)  # (no k-mers: an input that shares nothing)
+            elif min_count > 1 or max_count is not None:
+                ranged = engine.filtered_copy(dev, t, min_count, max_count)
+                engine.free_result(t)
+                t = ranged
+            tables.append(t)
+        ctable = engine.color_table(dev, tables)  # (frees each table as it is folded in)
+        gram, occ, private = engine.mask_gram(dev, ctable, nc)
+    finally:
+        for t in tables:
+            engine.free_result(t)
+        engine.free_result(ctable)
+    with open(output_path, "wb") as fh:
+        engine.emit_compare(labels, gram, k, fh)
+    if matrix_path is not None:
+        with open(matrix_path, "wb") as fh:
+            engine.emit_compare_matrix(labels, gram, k, metric or "dist", fh)
+    if occupancy_path is not None:
+        with open(occupancy_path, "wb") as fh:
+            engine.emit_occupancy(occ, fh)
+    if summary_path is not None:
+        with open(summary_path, "wb") as fh:
+            engine.emit_compare_summary(labels, gram, private, fh)
+    logging.info("That's all!")
+
+
+def _check_compare_options(k: int, inputs, labels, min_qual: int, fastq, min_count: int, max_count: Optional[int],
+                           output_path: str, matrix_path: Optional[str], metric: Optional[str],
+                           occupancy_path: Optional[str], summary_path: Optional[str]) -> None:
+    """What `kmer compare` refuses, before any device work or output."""
+    if k <= 1:
+        raise AssertionError("k must be >= 1, got %d instead." % k)
+    if k > engine.MAX_K:
+        raise AssertionError("kmer compare takes K <= %d (one 64-bit key per k-mer), got %d: word keys are a stated "
+                             "limit of this command" % (engine.MAX_K, k))
+    if not 2 <= len(inputs) <= engine.MAX_COLORS:
+        raise AssertionError("kmer compare takes 2 to %d INPUT, got %d" % (engine.MAX_COLORS, len(inputs)))
+    seen = set()
+    for lab in labels:
+        if "\t" in lab:
+            raise AssertionError("INPUT label %r holds a tab" % lab)
+        if lab in seen:
+            raise AssertionError("two INPUT have the label %r: labels must differ" % lab)
+        seen.add(lab)
+    if min_qual > 0 and not any(fastq):
+        raise AssertionError("--min-qual needs fastq input: no INPUT is fastq")
+    if max_count is not None and min_count > max_count:
+        raise AssertionError("--min-count %d is greater than --max-count %d" % (min_count, max_count))
+    if metric is not None and matrix_path is None:
+        raise AssertionError("--metric needs --matrix: it chooses the matrix's values")
+    named = [("OUTPUT", output_path)] + [(name, path) for name, path in (
+        ("--matrix", matrix_path), ("--occupancy", occupancy_path), ("--summary", summary_path)) if path is not None]
+    for i, (na, pa) in enumerate(named):
+        for path in inputs:
+            if _same_path(pa, path):
+                raise AssertionError("%s and an INPUT name the same file, %r" % (na, pa))
         for nb, pb in named[:i]:
             if _same_path(pa, pb):
                 raise AssertionError("%s and %s name the same file, %r" % (nb, na, pa))
