@@ -304,7 +304,13 @@ int kman_finish(kman_ctx *ctx, uint64_t *d_keys, uint64_t *d_keys_alt, void *d_v
  * kman_groups_plan gives the work-area size, or KMAN_EFALLBACK when the input
  * is outside the path (k > 25, too many k-mers for the region capacities).  kman_groups returns KMAN_EFALLBACK also when a region
  * overflowed (a strongly skewed prefix distribution); the outputs are then
- * undefined and the caller runs the general path.  d_okeys / d_ovals hold
+ * undefined and the caller runs the general path.  The capacities are three,
+ * each fixed by the plan: C0 items per pass-0 region (top 8 key bits, position
+ * segment), C1 items per pass-1 sub-region (region, chain) and 8704 items
+ * (FCAP) per finish region, its two sub-regions together.  A region filled
+ * to exactly its capacity is inside the path (KMAN_OK, every row exact); one
+ * more item is KMAN_EFALLBACK, nothing is written past a capacity, and the
+ * next call on the ctx starts clean.  d_okeys / d_ovals hold
  * up to n_bases x (RC ? 2 : 1) entries. */
 int kman_groups_plan(uint64_t n_bases, uint32_t k, uint32_t flags, int mode, uint64_t *work_bytes);
 int kman_groups(kman_ctx *ctx, const uint8_t *d_codes, uint64_t n_bases, uint32_t k, uint32_t flags, int mode,
