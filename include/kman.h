@@ -794,6 +794,115 @@ int kman_classify_pick(kman_ctx *ctx, const uint32_t *d_planes, uint64_t n_recor
 int kman_mask_gram(kman_ctx *ctx, const uint64_t *d_masks, uint64_t n, uint32_t n_colors, uint64_t *d_gram,
                    uint64_t *d_occ, uint64_t *d_private);
 
+/* ------------------------------------------------- unitigs of a count table
+ * Not in the reference: the compacted de Bruijn graph of a CANONICAL count
+ * table (`kmer unitigs`), whose nodes are the table's rows and whose
+ * non-branching paths are merged into unitigs.  k is odd, 3 <= k <= 31, so no
+ * k-mer is its own reverse complement.
+ *
+ * Definition.  Row i holds the canonical k-mer x_i (keys strictly ascending).
+ *   A row has two sides, KMAN_GRAPH_R (the right end of the canonical spelling)
+ *   and KMAN_GRAPH_L; the pair is packed as (row << 1) | side.
+ *   Neighbours of side R of x: for each base b, y = x[1:] + b; when c =
+ *   min(y, revcomp(y)) is a row, that row is a neighbour, entered at its side L
+ *   when y == c and at its side R otherwise.  Of side L: y = b + x[:-1],
+ *   entered at R when y == c, else at L.  deg(x, s) counts the bases that give
+ *   a neighbour; two bases that reach one row count twice.
+ *   Side (i, s) is LINKED to (j, t) when deg(i, s) == 1, its one neighbour is
+ *   (j, t), deg(j, t) == 1 and j != i.  Links are symmetric.
+ *   A UNITIG is a connected component of the links, a path or a cycle; a cycle
+ *   is cut at side L of its smallest row (that link and its partner go).  A
+ *   path starts at the end row with the smaller index.  Walking from there, a
+ *   row that is left through R is spelled as its key, one left through L as
+ *   the reverse complement (the last row is left through the side opposite
+ *   the one it was entered by, a lone row through R); the unitig's text is the
+ *   first row's k bases and the last base of every later row.  Unitigs are
+ *   ordered by their start row.
+ *
+ * kman_graph_links: d_tkeys, nt, k and the index that kman_table_index made of
+ *   these keys with this k and index_bits.  d_link, 2 nt u32, every word
+ *   written: d_link[2 i + s] = the packed partner of side s of row i, or
+ *   KMAN_GRAPH_NONE.  k even or outside 3..31, index_bits outside
+ *   1..min(2k, KMAN_SCREEN_MAX_INDEX_BITS), nt >= KMAN_GRAPH_MAX_ROWS or a NULL
+ *   pointer with nt > 0: KMAN_EINVAL, nothing written.  nt == 0: nothing is
+ *   done.  One thread per row: its 8 neighbour keys are looked up with the 8
+ *   searches advancing in lockstep, floor(log2(bucket rows)) + 1 key reads each
+ *   at most; a second launch applies the mutual rule.  An index that does not
+ *   belong to the table, or keys that are not ascending, give wrong links,
+ *   never a wild address or an endless loop (bounds are clamped to nt; every
+ *   search runs a step count fixed before it starts), and what is written is
+ *   still symmetric: d_link[v] == u wherever d_link[u] == v.  The inputs are
+ *   not written.  8 nt bytes of the context's scratch.  Launches are timed
+ *   under the tag "graph_links".  Synchronises.
+ *
+ * kman_graph_rank: d_link as kman_graph_links writes it (a word >= 2 nt reads
+ *   as KMAN_GRAPH_NONE), never written.  Three outputs of nt u32, every word
+ *   written:
+ *     d_start[i]  the start row of row i's unitig
+ *     d_pos[i]    (position of row i in the walk from the start << 1) |
+ *                 orientation: 0 = spelled as its key, 1 = reverse complement
+ *     d_nodes[i]  the unitig's rows when row i is its start, 0 otherwise
+ *   List ranking over the 2 nt states "leave row i through side s" by pointer
+ *   doubling, one launch per round over all states and a device word that
+ *   tells the host whether a pointer moved: at most ceil(log2(2 nt)) + 1
+ *   rounds, fewer when nothing moves earlier (a path of p rows: ceil(log2(p -
+ *   1)) rounds that move).  No kernel loops over a unitig.  States that then
+ *   point at no end lie on cycles: each cycle's smallest row comes from a
+ *   minimum carried through the rounds, its side-L link and the partner's are
+ *   cut in a private copy of the links, those states are set up again and the
+ *   rounds repeated.  *rounds (may be NULL): the rounds in which a pointer
+ *   moved, both passes; *cycles (may be NULL): the cycles cut.  nt == 0:
+ *   nothing is done, both are 0.  nt >= KMAN_GRAPH_MAX_ROWS or a NULL array
+ *   with nt > 0: KMAN_EINVAL, nothing written.  Links that are not symmetric
+ *   give wrong ranks within the same bounds and round counts.  56 nt + 16
+ *   bytes of the context's scratch.  Launches are timed under "graph_rank".
+ *   Synchronises (once per round).
+ *
+ * kman_unitig_spell: the table (d_tkeys, d_tcounts of count_bytes = 4 or 8,
+ *   nt, k) and kman_graph_rank's three arrays; none is written.  Outputs, for
+ *   *n_unitigs = U unitigs of *n_bases = B bases in all:
+ *     d_off     U + 1 u64: unitig u's text is d_seq[d_off[u], d_off[u + 1]);
+ *               d_off[U] = B
+ *     d_unodes  U u32: its rows (its text has that many + k - 1 bases)
+ *     d_kc      U u64: the sum of its rows' counts, modulo 2^64
+ *     d_seq     B bytes of ACGT, not terminated
+ *   in the order of the start rows.  All four NULL: only *n_unitigs and
+ *   *n_bases are set (the call that sizes the buffers; d_tkeys, d_tcounts and
+ *   d_start are then not read).  Else d_off holds unitig_cap + 1 words,
+ *   d_unodes and d_kc unitig_cap, d_seq seq_cap bytes; a capacity below U or B
+ *   is KMAN_ECAP with both numbers set and nothing written.  Some but not all
+ *   outputs NULL, k even or outside 3..31, count_bytes not 4 or 8, nt >=
+ *   KMAN_GRAPH_MAX_ROWS, a NULL input with nt > 0: KMAN_EINVAL, nothing
+ *   written.  nt == 0: both numbers are 0, nothing is launched or written.
+ *   One pass of tiles of KMAN_UNITIG_TILE rows counts the starts and sums their
+ *   bases (two block scans, two decoupled look-backs); then one thread per row
+ *   writes the row's own base (a start: its k bases, offset and rows) and adds
+ *   its count to d_kc with one 64-bit integer atomic: two calls give equal
+ *   bytes.  Rank arrays that are not kman_graph_rank's give wrong text within
+ *   the outputs' bounds.  12 nt + 8 bytes of the context's scratch.  Launches
+ *   are timed under "unitig_spell".  Synchronises.
+ *
+ * kman_format_unitigs (host): ">ID LN:i:BASES KC:i:SUM\nSEQ\n" per unitig, ID
+ *   = first_id + u in decimal, the sequence on one line.  seq, off (n + 1
+ *   words) and kc are host copies of kman_unitig_spell's outputs.  The
+ *   kman_format_* contract: *used is the size, KMAN_ECAP when cap is short or
+ *   out is NULL; n == 0 writes nothing. */
+#define KMAN_GRAPH_R 0
+#define KMAN_GRAPH_L 1
+#define KMAN_GRAPH_NONE 0xFFFFFFFFu
+#define KMAN_GRAPH_MAX_ROWS (1ull << 31)
+#define KMAN_UNITIG_TILE 2048
+int kman_graph_links(kman_ctx *ctx, const uint64_t *d_tkeys, uint64_t nt, uint32_t k, const uint64_t *d_index,
+                     uint32_t index_bits, uint32_t *d_link);
+int kman_graph_rank(kman_ctx *ctx, const uint32_t *d_link, uint64_t nt, uint32_t *d_start, uint32_t *d_pos,
+                    uint32_t *d_nodes, uint32_t *rounds, uint64_t *cycles);
+int kman_unitig_spell(kman_ctx *ctx, const uint64_t *d_tkeys, const void *d_tcounts, uint32_t count_bytes, uint64_t nt,
+                      uint32_t k, const uint32_t *d_start, const uint32_t *d_pos, const uint32_t *d_nodes,
+                      uint64_t *d_off, uint32_t *d_unodes, uint64_t *d_kc, uint64_t unitig_cap, uint8_t *d_seq,
+                      uint64_t seq_cap, uint64_t *n_unitigs, uint64_t *n_bases);
+int kman_format_unitigs(const uint8_t *seq, const uint64_t *off, const uint64_t *kc, uint64_t n, uint64_t first_id,
+                        char *out, size_t cap, size_t *used, int threads);
+
 /* ------------------------------------------- per-record order statistic
  * Not in the reference: one quantile (the median, by default) of the table
  * counts of a record's k-mer windows.  A sum commutes and an order statistic

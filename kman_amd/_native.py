@@ -66,6 +66,11 @@ KMAN_CLASSIFY_NONE = 0xFFFFFFFF  # kman_classify_pick: no colour has a hit
 KMAN_GRAM_THREADS = 256  # threads per block of kman_mask_gram (include/kman.h)
 KMAN_GRAM_MAX_BLOCKS = 1024  # its largest grid: one grid stride is KMAN_GRAM_MAX_BLOCKS * KMAN_GRAM_THREADS rows
 KMAN_GRAM_MAX_ROWS = 1 << 40  # more rows are refused (the kernel's 32-bit accumulators)
+KMAN_GRAPH_R = 0  # the sides of a row of kman_graph_links: the right end of the canonical spelling (include/kman.h)
+KMAN_GRAPH_L = 1  # and the left end; a (row, side) pair is packed as (row << 1) | side
+KMAN_GRAPH_NONE = 0xFFFFFFFF  # no partner
+KMAN_GRAPH_MAX_ROWS = 1 << 31  # tables of this many rows are refused (the packed u32 words)
+KMAN_UNITIG_TILE = 2048  # rows per tile of kman_unitig_spell's layout pass
 KMAN_MATCH_RIGHT = 0
 KMAN_MATCH_LEFT = 1
 KMAN_MATCH_MIN = 2
@@ -250,6 +255,17 @@ SIGNATURES = {
     ),
     "kman_classify_pick": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p]),
     "kman_mask_gram": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "kman_graph_links": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_uint32, c_void_p]),
+    "kman_graph_rank": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_uint32), POINTER(c_uint64)],
+    ),
+    "kman_unitig_spell": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, POINTER(c_uint64), POINTER(c_uint64)],
+    ),
+    "kman_format_unitigs": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_size_t, POINTER(c_size_t), c_int],
+    ),
     "kman_format_classify": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_char_p, c_void_p,
                 c_char_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t), c_int],

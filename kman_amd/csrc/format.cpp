@@ -542,6 +542,34 @@ extern "C" int kman_format_classify(const uint32_t *windows, const int32_t *assi
     return run_sliced(n_records, buf, cap, used, threads, size_of, write_at);
 }
 
+// ">%d LN:i:%d KC:i:%d\n%s\n" % (first_id + u, bases, kc, seq) per unitig, the
+// sequence on one line (`kmer unitigs`; not in the reference)
+extern "C" int kman_format_unitigs(const uint8_t *seq, const uint64_t *off, const uint64_t *kc, uint64_t n,
+                                   uint64_t first_id, char *out, size_t cap, size_t *used, int threads) {
+    if (!used || (n && (!seq || !off || !kc))) return KMAN_EINVAL;
+    for (uint64_t u = 0; u < n; u++)
+        if (off[u + 1] < off[u]) return KMAN_EINVAL;
+    auto size_of = [&](uint64_t u) -> size_t {
+        const uint64_t len = off[u + 1] - off[u];
+        return 1 + ndigits(first_id + u) + 6 + ndigits(len) + 6 + ndigits(kc[u]) + 1 + len + 1;
+    };
+    auto write_at = [&](uint64_t u, char *p) -> char * {
+        const uint64_t len = off[u + 1] - off[u];
+        *p++ = '>';
+        p = put_u64(p, first_id + u);
+        memcpy(p, " LN:i:", 6);
+        p = put_u64(p + 6, len);
+        memcpy(p, " KC:i:", 6);
+        p = put_u64(p + 6, kc[u]);
+        *p++ = '\n';
+        if (len) memcpy(p, seq + off[u], len);
+        p += len;
+        *p++ = '\n';
+        return p;
+    };
+    return run_sliced(n, out, cap, used, threads, size_of, write_at);
+}
+
 // k in 33..64: keys as (hi, lo) word pairs (kman_extract_wide)
 extern "C" int kman_format_count_wide(const uint64_t *hi, const uint64_t *lo, const void *counts, uint32_t count_bytes,
                                       uint64_t n, uint32_t k, char *out, size_t cap, size_t *used, int threads) {

@@ -1,0 +1,493 @@
+// unitig.hip — the compacted de Bruijn graph of a canonical count table: the
+// table's rows are the nodes, non-branching paths are merged into unitigs
+// (`kmer unitigs`; include/kman.h states the definition).
+//
+// kman_graph_links, one thread per row, two kernels:
+//   neighbours  the 4 keys that extend the row's k-mer to the right (side R)
+//               and the 4 that extend it to the left (side L) are folded to
+//               their canonical form and looked up through the prefix index of
+//               kman_table_index: the 8 searches advance in lockstep, as
+//               screen_lookup.h's table_lookup does, and a hit keeps the ROW
+//               its lower bound ended on.  A side with exactly one hit writes
+//               (row << 1 | side entered) to a scratch word, every other side
+//               KMAN_GRAPH_NONE.
+//   mutual      side u keeps its word v when v's own word is u and v is a side
+//               of another row; else KMAN_GRAPH_NONE.
+//
+// kman_graph_rank, list ranking over the 2 nt states "leave row i through side
+// s" (state 2 i + s): the successor of a state is its partner's opposite side,
+// a state without a link is terminal (it points at itself).  Pointer doubling
+// with the rounds driven from the host: a round reads (pointer, distance, least
+// row) of every state and of the state it points at from one buffer and writes
+// the other (no state is read and written in one launch), and sets a device
+// word when a pointer moved; the host stops when none did, after at most
+// ceil(log2(2 nt)) + 1 rounds.  No kernel holds a loop over a unitig.  States
+// that then do not point at a terminal lie on cycles: the least row carried
+// through the rounds names each cycle's smallest row, whose side-L link and its
+// partner are removed from a private copy of the links, those states alone are
+// set up again and the rounds repeated.  Per row the two states give the two
+// end rows of its path (the smaller one is the unitig's start), the distance
+// to each, and with that the position, the orientation and the node count.
+//
+// kman_unitig_spell, two kernels:
+//   layout   tiles of UTILE rows: the heads (position 0) are counted and their
+//            nodes + k - 1 bases summed, one block scan each, and the tile's
+//            two offsets come from two decoupled look-backs of common.h
+//            (dynamic tile ids; the second one in the upper half of the status
+//            words): every head gets its ordinal and its first base's offset.
+//   spell    one thread per row: a head writes its k bases and its unitig's
+//            offset and node count, every other row the one base it adds;
+//            every row adds its count to its unitig's KC with one 64-bit
+//            integer atomic (integer adds commute: two calls, equal bytes).
+//
+// Bounds, not values: every index read from memory (index pair, link, pointer,
+// start row, ordinal, offset) is compared with its array's size before it is
+// used, every search runs a step count fixed before it starts and every round
+// count is fixed by nt; a foreign index, unsorted keys or links that are no
+// links give wrong unitigs, never a wild address or an unbounded loop.
+//
+// Algorithmic bytes per row: links 8 B key, 8 index pairs, at most
+// 8 (floor(log2 bucket) + 1) random key reads, 8 + 24 B of link words; a rank
+// round 2 x (12 B read + 12 B random read + 12 B written); spell 24 B read,
+// two dependent random reads (ordinal, offset), one byte and one atomic.
+#include "common.h"
+#include "screen_lookup.h"
+
+namespace {
+
+constexpr int UT = 256;
+constexpr int UR = 8;  // consecutive rows per thread of the layout kernel
+constexpr int UTILE = UT * UR;
+constexpr uint32_t NONE = KMAN_GRAPH_NONE;
+static_assert(UTILE == KMAN_UNITIG_TILE, "include/kman.h states the tile size");
+static_assert(KMAN_GRAPH_R == 0 && KMAN_GRAPH_L == 1, "a state's opposite side is its word ^ 1");
+
+// the reverse complement of a 2k-bit key
+KMAN_DEV uint64_t rc_key(uint64_t x, uint32_t k) {
+    x = ~x;
+    x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
+    x = ((x >> 4) & 0x0f0f0f0f0f0f0f0full) | ((x & 0x0f0f0f0f0f0f0f0full) << 4);
+    return __builtin_bswap64(x) >> (64 - 2 * k);
+}
+
+// table_lookup of screen_lookup.h with the hit's ROW for its count: the same
+// clamping (lo <= hi <= nt, every key index < nt), the same fixed step count.
+// row[j] < nt for every j of the returned mask.
+template <int EI>
+KMAN_DEV uint32_t row_lookup(const uint64_t (&kf)[EI], uint32_t shift, const uint64_t *__restrict__ index,
+                             const uint64_t *__restrict__ tkeys, uint64_t nt, uint64_t (&row)[EI]) {
+    uint64_t lo[EI], len[EI];
+#pragma unroll
+    for (int j = 0; j < EI; j++) {
+        const uint64_t p = kf[j] >> shift;  // (kf < 2^2k: p < 2^index_bits)
+        lo[j] = index[p];
+        len[j] = index[p + 1];
+    }
+    uint32_t nsteps = 0;
+#pragma unroll
+    for (int j = 0; j < EI; j++) {
+        const uint64_t hi = smin64(len[j], nt);  // lo <= hi <= nt whatever the index holds
+        lo[j] = smin64(lo[j], hi);
+        len[j] = hi - lo[j];
+        const uint32_t s = steps_of(len[j]);
+        nsteps = s > nsteps ? s : nsteps;
+    }
+    uint32_t hit = 0;
+    for (uint32_t s = 0; s < nsteps; s++) {  // (nsteps <= 64)
+        uint64_t v[EI];
+#pragma unroll
+        for (int j = 0; j < EI; j++) v[j] = len[j] ? tkeys[lo[j] + (len[j] >> 1)] : 0;  // (lo + half < lo + len <= nt)
+#pragma unroll
+        for (int j = 0; j < EI; j++) {
+            const uint64_t half = len[j] >> 1;
+            const bool on = len[j] != 0;
+            hit |= (uint32_t)(on && v[j] == kf[j]) << j;
+            if (on && v[j] < kf[j]) {
+                lo[j] += half + 1;
+                len[j] -= half + 1;
+            } else {
+                len[j] = half;
+            }
+        }
+    }
+    uint32_t ok = 0;  // a hit's row is where its lower bound ended
+#pragma unroll
+    for (int j = 0; j < EI; j++) {
+        row[j] = lo[j];
+        ok |= (uint32_t)(((hit >> j) & 1u) && lo[j] < nt) << j;
+    }
+    return ok;
+}
+
+// ---------------------------------------------------------------- links
+__global__ __launch_bounds__(UT) void neighbours_kernel(const uint64_t *__restrict__ tkeys, uint32_t nt, uint32_t k,
+                                                        const uint64_t *__restrict__ index, uint32_t shift,
+                                                        uint32_t *__restrict__ nb) {
+    const uint32_t i = blockIdx.x * UT + threadIdx.x;
+    if (i >= nt) return;
+    const uint64_t mask = (1ull << (2 * k)) - 1;  // (k <= 31)
+    const uint64_t x = tkeys[i] & mask;
+    uint64_t kf[8], row[8];
+    uint32_t fwd = 0;  // bit j: the extension is its own canonical form
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint64_t b = (uint64_t)(j & 3);
+        const uint64_t y = j < 4 ? (((x << 2) | b) & mask) : ((x >> 2) | (b << (2 * k - 2)));
+        const uint64_t r = rc_key(y, k);
+        kf[j] = y < r ? y : r;
+        fwd |= (uint32_t)(y < r) << j;
+    }
+    const uint32_t hit = row_lookup<8>(kf, shift, index, tkeys, (uint64_t)nt, row);
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        const uint32_t h = (hit >> (4 * s)) & 15u;
+        uint32_t w = NONE;
+        if (__popc(h) == 1) {
+            const int j = 4 * s + (__ffs((int)h) - 1);
+            uint64_t rj = 0;
+#pragma unroll
+            for (int q = 0; q < 8; q++) rj = q == j ? row[q] : rj;  // (no indexed register array)
+            // out of R a forward neighbour is entered at its L, a reversed one at its R; out of L the other way
+            const uint32_t f = (fwd >> j) & 1u;
+            const uint32_t t = s == KMAN_GRAPH_R ? (f ? KMAN_GRAPH_L : KMAN_GRAPH_R) : (f ? KMAN_GRAPH_R : KMAN_GRAPH_L);
+            w = ((uint32_t)rj << 1) | t;  // (rj < nt < 2^31)
+        }
+        nb[2 * (uint64_t)i + s] = w;
+    }
+}
+
+__global__ __launch_bounds__(UT) void mutual_kernel(const uint32_t *__restrict__ nb, uint32_t n2,
+                                                    uint32_t *__restrict__ link) {
+    const uint32_t u = blockIdx.x * UT + threadIdx.x;
+    if (u >= n2) return;
+    const uint32_t v = nb[u];
+    const bool ok = v < n2 && (v >> 1) != (u >> 1) && nb[v] == u;
+    link[u] = ok ? v : NONE;
+}
+
+// ----------------------------------------------------------------- rank
+// a state's word: its pointer in the low half, the distance to it in the high half
+KMAN_DEV uint32_t ptr_of(uint64_t s, uint32_t self, uint32_t n2) {
+    const uint32_t p = (uint32_t)s;
+    return p < n2 ? p : self;
+}
+
+__global__ __launch_bounds__(UT) void rank_init_kernel(const uint32_t *__restrict__ link, uint32_t n2,
+                                                       uint32_t *__restrict__ mine, uint64_t *__restrict__ S,
+                                                       uint32_t *__restrict__ M) {
+    const uint32_t u = blockIdx.x * UT + threadIdx.x;
+    if (u >= n2) return;
+    const uint32_t l = link[u];
+    const bool on = l < n2;
+    mine[u] = on ? l : NONE;
+    S[u] = on ? ((uint64_t)(l ^ 1u) | (1ull << 32)) : (uint64_t)u;
+    M[u] = u >> 1;
+}
+
+__global__ __launch_bounds__(UT) void rank_round_kernel(const uint64_t *__restrict__ S, const uint32_t *__restrict__ M,
+                                                        uint32_t n2, uint64_t *__restrict__ S2,
+                                                        uint32_t *__restrict__ M2, uint32_t *__restrict__ moved) {
+    const uint32_t u = blockIdx.x * UT + threadIdx.x;
+    bool mv = false;
+    if (u < n2) {
+        const uint64_t s = S[u];
+        const uint32_t p = ptr_of(s, u, n2);
+        const uint64_t t = S[p];
+        const uint32_t q = ptr_of(t, p, n2);
+        const uint32_t a = M[u], b = M[p];
+        // (the distance wraps on a cycle alone, where it is never used)
+        S2[u] = (uint64_t)q | ((uint64_t)((uint32_t)(s >> 32) + (uint32_t)(t >> 32)) << 32);
+        M2[u] = a < b ? a : b;
+        mv = q != p;
+    }
+    if (__ballot(mv) != 0 && lane_id() == 0) *moved = 1u;
+}
+
+// row i is its cycle's smallest: its side-L link and the partner's go
+__global__ __launch_bounds__(UT) void cycle_cut_kernel(const uint32_t *__restrict__ link, const uint64_t *__restrict__ S,
+                                                       const uint32_t *__restrict__ M, uint32_t nt,
+                                                       uint32_t *__restrict__ mine, uint32_t *__restrict__ ncut) {
+    const uint32_t i = blockIdx.x * UT + threadIdx.x;
+    if (i >= nt) return;
+    const uint32_t n2 = 2 * nt, u = 2 * i + KMAN_GRAPH_L;
+    const uint32_t p = ptr_of(S[u], u, n2);
+    if (link[p] >= n2 || M[u] != i) return;  // (points at a terminal: a path)
+    const uint32_t q = mine[u];
+    mine[u] = NONE;
+    if (q < n2) mine[q] = NONE;
+    atomicAdd(ncut, 1u);
+}
+
+// the states that point at no terminal start again from the cut links
+__global__ __launch_bounds__(UT) void rank_again_kernel(const uint32_t *__restrict__ link,
+                                                        const uint32_t *__restrict__ mine, uint32_t n2,
+                                                        uint64_t *__restrict__ S, uint32_t *__restrict__ M) {
+    const uint32_t u = blockIdx.x * UT + threadIdx.x;
+    if (u >= n2) return;
+    const uint32_t p = ptr_of(S[u], u, n2);
+    if (link[p] >= n2) return;
+    const uint32_t l = mine[u];
+    S[u] = l < n2 ? ((uint64_t)(l ^ 1u) | (1ull << 32)) : (uint64_t)u;
+    M[u] = u >> 1;
+}
+
+__global__ __launch_bounds__(UT) void rank_finish_kernel(const uint64_t *__restrict__ S, uint32_t nt,
+                                                         uint32_t *__restrict__ start, uint32_t *__restrict__ pos,
+                                                         uint32_t *__restrict__ nodes) {
+    const uint32_t i = blockIdx.x * UT + threadIdx.x;
+    if (i >= nt) return;
+    const uint32_t n2 = 2 * nt;
+    const uint64_t sr = S[2 * i + KMAN_GRAPH_R], sl = S[2 * i + KMAN_GRAPH_L];
+    const uint32_t er = ptr_of(sr, 2 * i, n2) >> 1, el = ptr_of(sl, 2 * i + 1, n2) >> 1;  // the end rows
+    const uint32_t dr = (uint32_t)(sr >> 32), dl = (uint32_t)(sl >> 32);
+    // the start lies behind side L: the walk leaves this row through R, the canonical spelling
+    const bool canon = el <= er;
+    const uint32_t p = canon ? dl : dr;
+    start[i] = canon ? el : er;
+    pos[i] = (p << 1) | (canon ? 0u : 1u);
+    nodes[i] = p == 0 ? dr + dl + 1 : 0u;
+}
+
+// ---------------------------------------------------------------- spell
+__global__ __launch_bounds__(UT) void layout_kernel(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ nodes,
+                                                    uint32_t nt, uint32_t k, uint32_t *__restrict__ ord,
+                                                    uint64_t *__restrict__ hoff, uint64_t *status, uint64_t n_tiles,
+                                                    uint32_t *counter, uint32_t epoch, uint32_t *err) {
+    __shared__ uint32_t lds_c[UT / 64];
+    __shared__ uint64_t lds_b[UT / 64];
+    __shared__ uint64_t lds_base[2];
+    __shared__ uint32_t lds_tile;
+    const int64_t tile = grab_tile(counter, &lds_tile);
+    const uint64_t r0 = (uint64_t)tile * UTILE + (uint64_t)threadIdx.x * UR;
+    uint32_t heads = 0, nn[UR];
+    uint64_t bases = 0;
+#pragma unroll
+    for (int r = 0; r < UR; r++) {
+        const uint64_t i = r0 + r;
+        const bool head = i < nt && (pos[i < nt ? i : 0] >> 1) == 0;
+        nn[r] = head ? nodes[i] : 0u;
+        heads |= (uint32_t)head << r;
+        bases += head ? (uint64_t)nn[r] + (k - 1) : 0ull;
+    }
+    uint32_t tc = 0;
+    uint64_t tb = 0;
+    uint32_t c = block_exclusive_scan<UT>((uint32_t)__popc(heads), SumU32(), 0u, lds_c, &tc);
+    uint64_t b = block_exclusive_scan<UT>(bases, SumU64(), (uint64_t)0, lds_b, &tb);
+    if ((threadIdx.x >> 6) == 0) {
+        const uint64_t bc = wave_lookback<0>(status, tile, (uint64_t)tc, epoch, err);
+        const uint64_t bb = wave_lookback<0>(status + n_tiles, tile, tb, epoch, err);
+        if (lane_id() == 0) {
+            lds_base[0] = bc;
+            lds_base[1] = bb;
+        }
+    }
+    __syncthreads();
+    c += (uint32_t)lds_base[0];
+    b += lds_base[1];
+#pragma unroll
+    for (int r = 0; r < UR; r++) {
+        const uint64_t i = r0 + r;
+        if (i >= nt) break;
+        const bool head = (heads >> r) & 1u;
+        ord[i] = head ? c : NONE;
+        if (head) {
+            hoff[i] = b;
+            c++;
+            b += (uint64_t)nn[r] + (k - 1);
+        }
+    }
+}
+
+template <typename CT>
+__global__ __launch_bounds__(UT) void spell_kernel(const uint64_t *__restrict__ tkeys, const CT *__restrict__ tcounts,
+                                                   uint32_t nt, uint32_t k, const uint32_t *__restrict__ start,
+                                                   const uint32_t *__restrict__ pos, const uint32_t *__restrict__ nodes,
+                                                   const uint32_t *__restrict__ ord, const uint64_t *__restrict__ hoff,
+                                                   uint64_t nu, uint64_t total, uint64_t *__restrict__ off,
+                                                   uint32_t *__restrict__ unodes, unsigned long long *__restrict__ kc,
+                                                   uint8_t *__restrict__ seq) {
+    const uint32_t i = blockIdx.x * UT + threadIdx.x;
+    if (i >= nt) return;
+    if (i == 0) off[nu] = total;
+    const uint32_t a = start[i];
+    if (a >= nt) return;
+    const uint32_t o = ord[a];
+    if ((uint64_t)o >= nu) return;  // (NONE: the start is no head; cannot happen on kman_graph_rank's output)
+    const uint64_t at = hoff[a];
+    const uint32_t pw = pos[i], p = pw >> 1;
+    const uint64_t x = tkeys[i] & ((1ull << (2 * k)) - 1);
+    const uint64_t s = (pw & 1u) ? rc_key(x, k) : x;
+    const uint32_t B = 0x54474341u;  // "ACGT"
+    if (p == 0) {
+        off[o] = at;
+        unodes[o] = nodes[i];
+        for (uint32_t j = 0; j < k; j++)  // (k <= 31)
+            if (at + j < total) seq[at + j] = (uint8_t)(B >> (8 * ((s >> (2 * (k - 1 - j))) & 3u)));
+    } else {
+        const uint64_t w = at + (k - 1) + p;
+        if (w < total) seq[w] = (uint8_t)(B >> (8 * (s & 3u)));
+    }
+    atomicAdd(&kc[o], (unsigned long long)tcounts[i]);
+}
+
+inline uint32_t blocks_of(uint64_t n) { return (uint32_t)ceil_div(n, UT); }
+
+int graph_args(kman_ctx *ctx, const char *who, uint64_t nt) {
+    if (nt >= KMAN_GRAPH_MAX_ROWS)
+        return kman_fail(ctx, KMAN_EINVAL, "%s: %llu rows, a packed (row, side) word takes fewer than 2^31", who,
+                         (unsigned long long)nt);
+    return KMAN_OK;
+}
+
+}  // namespace
+
+extern "C" int kman_graph_links(kman_ctx *ctx, const uint64_t *d_tkeys, uint64_t nt, uint32_t k,
+                                const uint64_t *d_index, uint32_t index_bits, uint32_t *d_link) {
+    if (!ctx) return KMAN_EINVAL;
+    if (k < 3 || k > 31 || (k & 1u) == 0)
+        return kman_fail(ctx, KMAN_EINVAL, "kman_graph_links: k must be odd and in [3, 31], got %u", k);
+    if (!index_bits_ok(k, index_bits))
+        return kman_fail(ctx, KMAN_EINVAL, "index_bits must be in [1, min(2k, %d)], got %u (k = %u)",
+                         KMAN_SCREEN_MAX_INDEX_BITS, index_bits, k);
+    KMAN_TRY(graph_args(ctx, "kman_graph_links", nt));
+    if (nt == 0) return KMAN_OK;
+    if (!d_tkeys || !d_index || !d_link) return kman_fail(ctx, KMAN_EINVAL, "kman_graph_links: null buffer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void *scr = nullptr;
+    KMAN_TRY(kman_scratch(ctx, (size_t)8 * nt, &scr));
+    uint32_t *nb = (uint32_t *)scr;
+    {
+        KTimer kt_(ctx, "graph_links");
+        hipLaunchKernelGGL(neighbours_kernel, dim3(blocks_of(nt)), dim3(UT), 0, ctx->stream, d_tkeys, (uint32_t)nt, k,
+                           d_index, 2 * k - index_bits, nb);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(mutual_kernel, dim3(blocks_of(2 * nt)), dim3(UT), 0, ctx->stream, nb, (uint32_t)(2 * nt),
+                           d_link);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KMAN_OK;
+}
+
+extern "C" int kman_graph_rank(kman_ctx *ctx, const uint32_t *d_link, uint64_t nt, uint32_t *d_start, uint32_t *d_pos,
+                               uint32_t *d_nodes, uint32_t *rounds, uint64_t *cycles) {
+    if (!ctx) return KMAN_EINVAL;
+    KMAN_TRY(graph_args(ctx, "kman_graph_rank", nt));
+    if (rounds) *rounds = 0;
+    if (cycles) *cycles = 0;
+    if (nt == 0) return KMAN_OK;
+    if (!d_link || !d_start || !d_pos || !d_nodes) return kman_fail(ctx, KMAN_EINVAL, "kman_graph_rank: null buffer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t n2 = (uint32_t)(2 * nt);
+    // scratch: two flag words, two state buffers, two least-row buffers, the links' copy
+    void *scr = nullptr;
+    KMAN_TRY(kman_scratch(ctx, 16 + (size_t)n2 * (8 + 8 + 4 + 4 + 4), &scr));
+    uint32_t *flags = (uint32_t *)scr;  // [0]: a pointer moved; [1]: cycles cut
+    uint64_t *S[2] = {(uint64_t *)((char *)scr + 16), (uint64_t *)((char *)scr + 16) + n2};
+    uint32_t *M[2] = {(uint32_t *)(S[1] + n2), (uint32_t *)(S[1] + n2) + n2};
+    uint32_t *mine = M[1] + n2;
+    uint32_t max_rounds = 1;  // ceil(log2(2 nt)) + 1
+    while ((1ull << (max_rounds - 1)) < n2) max_rounds++;
+    int cur = 0;
+    uint32_t done = 0;
+    uint32_t *h = (uint32_t *)ctx->h_small;
+    auto run_rounds = [&]() -> int {
+        for (uint32_t r = 0; r < max_rounds; r++) {
+            HIP_TRY(ctx, hipMemsetAsync(flags, 0, 4, ctx->stream));
+            hipLaunchKernelGGL(rank_round_kernel, dim3(blocks_of(n2)), dim3(UT), 0, ctx->stream, S[cur], M[cur], n2,
+                               S[cur ^ 1], M[cur ^ 1], flags);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemcpyAsync(h, flags, 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            cur ^= 1;  // (a round in which nothing moved copied the states)
+            if (h[0] == 0) break;
+            done++;
+        }
+        return KMAN_OK;
+    };
+    {
+        KTimer kt_(ctx, "graph_rank");
+        HIP_TRY(ctx, hipMemsetAsync(flags, 0, 16, ctx->stream));
+        hipLaunchKernelGGL(rank_init_kernel, dim3(blocks_of(n2)), dim3(UT), 0, ctx->stream, d_link, n2, mine, S[0],
+                           M[0]);
+        HIP_TRY(ctx, hipGetLastError());
+        KMAN_TRY(run_rounds());
+        hipLaunchKernelGGL(cycle_cut_kernel, dim3(blocks_of(nt)), dim3(UT), 0, ctx->stream, d_link, S[cur], M[cur],
+                           (uint32_t)nt, mine, flags + 1);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(h, flags + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const uint32_t ncut = h[0];
+        if (cycles) *cycles = ncut;
+        if (ncut) {
+            hipLaunchKernelGGL(rank_again_kernel, dim3(blocks_of(n2)), dim3(UT), 0, ctx->stream, d_link, mine, n2,
+                               S[cur], M[cur]);
+            HIP_TRY(ctx, hipGetLastError());
+            KMAN_TRY(run_rounds());
+        }
+        hipLaunchKernelGGL(rank_finish_kernel, dim3(blocks_of(nt)), dim3(UT), 0, ctx->stream, S[cur], (uint32_t)nt,
+                           d_start, d_pos, d_nodes);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (rounds) *rounds = done;
+    return KMAN_OK;
+}
+
+extern "C" int kman_unitig_spell(kman_ctx *ctx, const uint64_t *d_tkeys, const void *d_tcounts, uint32_t count_bytes,
+                                 uint64_t nt, uint32_t k, const uint32_t *d_start, const uint32_t *d_pos,
+                                 const uint32_t *d_nodes, uint64_t *d_off, uint32_t *d_unodes, uint64_t *d_kc,
+                                 uint64_t unitig_cap, uint8_t *d_seq, uint64_t seq_cap, uint64_t *n_unitigs,
+                                 uint64_t *n_bases) {
+    if (!ctx || !n_unitigs || !n_bases) return KMAN_EINVAL;
+    if (k < 3 || k > 31 || (k & 1u) == 0)
+        return kman_fail(ctx, KMAN_EINVAL, "kman_unitig_spell: k must be odd and in [3, 31], got %u", k);
+    if (count_bytes != 4 && count_bytes != 8) return kman_fail(ctx, KMAN_EINVAL, "count widths must be 4 or 8 bytes");
+    KMAN_TRY(graph_args(ctx, "kman_unitig_spell", nt));
+    const bool count_only = !d_off && !d_unodes && !d_kc && !d_seq;
+    if (!count_only && (!d_off || !d_unodes || !d_kc || !d_seq))
+        return kman_fail(ctx, KMAN_EINVAL, "kman_unitig_spell: the four outputs go together (all, or none to count)");
+    *n_unitigs = *n_bases = 0;
+    if (nt == 0) return KMAN_OK;
+    if (!d_pos || !d_nodes || (!count_only && (!d_tkeys || !d_tcounts || !d_start)))
+        return kman_fail(ctx, KMAN_EINVAL, "kman_unitig_spell: null buffer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void *scr = nullptr;
+    KMAN_TRY(kman_scratch(ctx, (size_t)12 * nt + 8, &scr));
+    uint64_t *hoff = (uint64_t *)scr;
+    uint32_t *ord = (uint32_t *)(hoff + nt);
+    const uint64_t T = ceil_div(nt, UTILE);
+    uint64_t nu = 0, total = 0;
+    {
+        KTimer kt_(ctx, "unitig_spell");
+        uint32_t epoch, *counter;
+        KMAN_TRY(kman_lookback_begin(ctx, 2 * T, &epoch, &counter));
+        hipLaunchKernelGGL(layout_kernel, dim3((uint32_t)T), dim3(UT), 0, ctx->stream, d_pos, d_nodes, (uint32_t)nt, k,
+                           ord, hoff, ctx->d_status, T, counter, epoch, ctx->d_err);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    KMAN_TRY(kman_lookback_total(ctx, T, &nu));
+    KMAN_TRY(kman_lookback_total(ctx, 2 * T, &total));
+    *n_unitigs = nu;
+    *n_bases = total;
+    if (count_only) return KMAN_OK;
+    if (nu > unitig_cap || total > seq_cap)
+        return kman_fail(ctx, KMAN_ECAP, "kman_unitig_spell: %llu unitigs of %llu bases for capacities %llu and %llu",
+                         (unsigned long long)nu, (unsigned long long)total, (unsigned long long)unitig_cap,
+                         (unsigned long long)seq_cap);
+    HIP_TRY(ctx, hipMemsetAsync(d_kc, 0, (size_t)8 * nu, ctx->stream));
+    {
+        KTimer kt_(ctx, "unitig_spell");
+        if (count_bytes == 4)
+            hipLaunchKernelGGL((spell_kernel<uint32_t>), dim3(blocks_of(nt)), dim3(UT), 0, ctx->stream, d_tkeys,
+                               (const uint32_t *)d_tcounts, (uint32_t)nt, k, d_start, d_pos, d_nodes, ord, hoff, nu,
+                               total, d_off, d_unodes, (unsigned long long *)d_kc, d_seq);
+        else
+            hipLaunchKernelGGL((spell_kernel<uint64_t>), dim3(blocks_of(nt)), dim3(UT), 0, ctx->stream, d_tkeys,
+                               (const uint64_t *)d_tcounts, (uint32_t)nt, k, d_start, d_pos, d_nodes, ord, hoff, nu,
+                               total, d_off, d_unodes, (unsigned long long *)d_kc, d_seq);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KMAN_OK;
+}

@@ -360,6 +360,16 @@ def compare_max_count():
                         help="Compare only k-mers seen at most this often in their own input. Default: no limit")
 
 
+def unitig_min_count():
+    return click.option("--min-count", "-L", "min_count", type=click.IntRange(min=1), default=1,
+                        help="Build the graph only of k-mers seen at least this often in INPUT. Default: 1 (all)")
+
+
+def unitig_max_count():
+    return click.option("--max-count", "-U", "max_count", type=click.IntRange(min=1), default=None,
+                        help="Build the graph only of k-mers seen at most this often in INPUT. Default: no limit")
+
+
 def matrix():
     return click.option("--matrix", "matrix_path", type=click.Path(dir_okay=False, writable=True), default=None,
                         metavar="FILE",

@@ -2,8 +2,8 @@
 
 Same arguments, flags, defaults, outputs and errors as the reference CLI; the
 work runs on the GPU through kman_amd (FastaBatcher.do + KJoiner.join).
-``hist``, ``sets``, ``screen``, ``classify`` and ``compare`` are this engine's
-own commands.
+``hist``, ``sets``, ``screen``, ``classify``, ``compare`` and ``unitigs`` are
+this engine's own commands.
 """
 
 from __future__ import annotations
@@ -1117,6 +1117,86 @@ def _check_compare_options(k: int, inputs, labels, min_qual: int, fastq, min_cou
         for nb, pb in named[:i]:
             if _same_path(pa, pb):
                 raise AssertionError("%s and %s name the same file, %r" % (nb, na, pa))
+
+
+@main.command(name="unitigs", context_settings=CONTEXT_SETTINGS, help="""
+Compact the k-mers of INPUT into maximal unitigs: the compacted de Bruijn
+graph's nodes, written to OUTPUT as FASTA, one
+">ID LN:i:BASES KC:i:SUM" line and one unwrapped sequence line per unitig
+(ID: the unitig's number from 0; SUM: the sum of its k-mers' counts).
+
+Not part of the reference kman CLI.  INPUT is counted on the GPU into a table
+of canonical k-mers, min(k-mer, reverse complement), always; each k-mer's
+eight possible neighbours are looked up in that table, paths without a branch
+are ranked by pointer doubling and spelled there (kman_graph_links,
+kman_graph_rank, kman_unitig_spell); the table never goes through a text file.
+Every k-mer of the table lies in exactly one unitig; a cycle is opened at its
+smallest k-mer; unitigs are ordered by their smallest end k-mer, so the same
+table gives the same bytes.  INPUT: a fasta or fastq file, plain or gzipped.
+K is odd and in 3..31.  -L / -U select the k-mers that become nodes (-L 2
+drops the k-mers a read set holds once, and with them the tips and bubbles of
+sequencing errors).  An INPUT without k-mers writes an empty OUTPUT; OUTPUT is
+never compressed.
+Out of scope: GFA links between unitigs, colours, K > 31, and tables larger
+than one GPU.
+Launched one process per GPU, the command runs on rank 0 alone.
+""")
+@args.input_path()
+@args.output_path(file_okay=True)
+@args.k()
+@args.input_format()
+@args.min_qual()
+@args.phred_offset()
+@args.unitig_min_count()
+@args.unitig_max_count()
+@args.index_bits()
+@args.hpc()
+def unitigs(input_path: str, output_path: str, k: int, input_format: str = "auto", min_qual: int = 0,
+            phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None,
+            index_bits: Optional[int] = None, hpc: bool = False) -> None:
+    input_file_exists(input_path)
+    fastq = _is_fastq(input_path, input_format)
+    _check_unitig_options(k, output_path, input_path, min_qual, fastq, min_count, max_count, index_bits)
+    if launch.distributed() and not launch.solo_rank():
+        launch.log_solo("kmer unitigs")  # (the table and its graph on one GPU, as kmer screen)
+        return
+    dev = engine.default_device()
+    table = None
+    try:
+        p = _parse_input(dev, input_path, input_format, min_qual if fastq else 0, int(phred_offset), hpc)
+        try:
+            engine.check_empty_names(p, k)
+            table = engine.join_groups(p, k, False, "count", canonical=True)
+        finally:
+            p.free()
+        if table is None:
+            table = engine.empty_count(dev, k)  # (no k-mers: no unitigs, an empty file)
+        elif min_count > 1 or max_count is not None:
+            ranged = engine.filtered_copy(dev, table, min_count, max_count)
+            engine.free_result(table)
+            table = ranged
+        res = engine.unitigs(dev, table, index_bits=index_bits)
+    finally:
+        engine.free_result(table)
+    with open(output_path, "wb") as fh:
+        engine.emit_unitigs(res, fh)
+    logging.info("That's all!")
+
+
+def _check_unitig_options(k: int, output_path: str, input_path: str, min_qual: int, fastq: bool, min_count: int,
+                          max_count: Optional[int], index_bits: Optional[int]) -> None:
+    """What `kmer unitigs` refuses, before any device work or output."""
+    engine.check_unitig_k(k)
+    if output_path.endswith(".gz"):
+        raise AssertionError("kmer unitigs writes plain text: OUTPUT %r ends in .gz" % output_path)
+    if _same_path(output_path, input_path):
+        raise AssertionError("OUTPUT and INPUT name the same file, %r" % output_path)
+    if min_qual > 0 and not fastq:
+        raise AssertionError("--min-qual needs fastq input")
+    if max_count is not None and min_count > max_count:
+        raise AssertionError("--min-count %d is greater than --max-count %d" % (min_count, max_count))
+    if index_bits is not None and index_bits > 2 * k:
+        raise AssertionError("--index-bits %d is more than the 2 K = %d bits of a k-mer" % (index_bits, 2 * k))
 
 
 if __name__ == "__main__":
