@@ -116,7 +116,7 @@ def test_vectorised_names_equal_title_name(nl, monkeypatch):
     hdr = np.asarray(hdr, dtype=np.uint64)
     want = [engine._title_name(text, int(h)) for h in hdr]
     for rows in (1 << 16, 300):  # one numpy block, several
-        monkeypatch.setattr(engine, "_NAME_ROWS", rows)
+        monkeypatch.setattr(engine.parsed, "_NAME_ROWS", rows)
         blob, off = engine.fastq_names(text, hdr)
         names = engine.BlobNames(blob, off)
         assert list(names) == want and names == want and len(names) == len(want)

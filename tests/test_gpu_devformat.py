@@ -61,7 +61,7 @@ def test_count_rows_device_equals_host(dev, cb, k, chunk, monkeypatch):
     from kman_amd import engine
 
     if chunk:
-        monkeypatch.setattr(engine, "_FMT_CHUNK", chunk)
+        monkeypatch.setattr(engine.output, "_FMT_CHUNK", chunk)
     rng = np.random.default_rng(k * 10 + cb)
     n = 20011
     keys = rng.integers(0, 1 << min(63, 2 * k), n, dtype=np.uint64)

@@ -406,7 +406,7 @@ def test_engine_cut_records_fastq_in_slices(dev, tmp_path, monkeypatch):
     path.write_bytes(text)
     for slice_bytes in (None, 4096):  # (4096: several slices, the big read in a slice of its own)
         if slice_bytes:
-            monkeypatch.setattr(engine, "_FMT_SLICE", slice_bytes)
+            monkeypatch.setattr(engine.device, "_FMT_SLICE", slice_bytes)
         for p in (engine.parse(dev, text, keep_text=True), engine.parse_file(dev, str(path), keep_text=True)):
             try:
                 assert p.n_records == R and p.rec_hdr.tolist() == off[:-1]

@@ -124,7 +124,7 @@ def test_host_formatter_agrees_with_the_statement(monkeypatch, tmp_path):
     # slices of a few unitigs each: the IDs go on counting
     records, k, _ = CASES["all_5mers"]
     units = uc.unitigs(uc.table_of(records, k))
-    monkeypatch.setattr(engine, "_UNITIG_SLICE", 37)
+    monkeypatch.setattr(engine.unitig, "_UNITIG_SLICE", 37)
     assert engine.emit_unitigs(_result(units, k)) == uc.text(units)
     # counts up to 2^64 - 1, first_id, and the formatter's own refusals
     big = [("ACGTA", 1, (1 << 64) - 1), ("CC", 1, 0)]
