@@ -273,7 +273,21 @@ int kman_sort_range(kman_ctx *ctx, uint64_t *d_keys, uint64_t *d_keys_alt, void 
  *          (oval_bytes == val_bytes)
  * Input: keys stably sorted by bits [lo_bit, key_bits).  In COUNT / UNIQ mode
  * the input arrays are scratch afterwards (segments longer than a chunk's
- * staging area are sorted in place through d_*_alt-free temporary buffers). */
+ * staging area are sorted in place through d_*_alt-free temporary buffers).
+ *
+ * kman_finish takes every 0 <= lo_bit <= key_bits <= 64.  lo_bit == 0: the
+ * input is fully sorted and every segment is one group (kman_split_bits
+ * gives 0 from n >= 513 * 2^(key_bits - 1) on); lo_bit == key_bits: no prefix,
+ * the whole array is one segment.  The input must be stably sorted by
+ * key >> lo_bit (the payload of equal prefixes in input order); the order
+ * within a prefix is free.  The array is read in chunks of 5120 keys; a chunk
+ * owns the segments that start in it and stages them in LDS.  A segment is
+ * re-sorted through the fallback (kman_sort on a temporary copy, then a
+ * second run of the kernel) exactly when it is the last one its chunk owns
+ * and ends at chunk offset 6144 or beyond, i.e. start offset + length >= 6144:
+ * 1025 keys at offset 5119 is the shortest.  Outputs are written to rows
+ * [0, *n_out) only; d_okeys / d_ovals hold n rows.  tests/finish_cases.py
+ * plan() is the executable statement of the per-chunk rules. */
 int kman_split_bits(uint64_t n, uint32_t key_bits, uint32_t *lo_bit);
 
 /* kman_extract + kman_sort_range(lo_bit, 2k) in one call: the first prefix

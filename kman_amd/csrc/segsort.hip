@@ -16,8 +16,11 @@
 // decoupled look-back per chunk.  Equal keys always share a segment, so every
 // group is decided inside one chunk, except inside "big" segments.
 //
-// Big segments (longer than the owner's region, FR - start offset > FC - 1
-// keys) cannot be staged.  The first run records their starts; the host then
+// Big segments cannot be staged: the last segment a chunk owns is big when it
+// ends at chunk offset FR or beyond (start offset + length >= FR; the tail
+// search stops at offset FR - 1, so the shortest one is FR - FC + 1 keys at
+// offset FC - 1).  tests/finish_cases.py plan() restates the rule and the
+// sort path of every chunk.  The first run records their starts; the host then
 // sorts them out of place with the full-key kman_sort (gathered contiguously:
 // their prefixes ascend, so the concatenation sorts into the same order) and
 // scatters them back, and a second run treats them as presorted slices that
@@ -383,14 +386,15 @@ __global__ __launch_bounds__(FT) void segfin_kernel(uint64_t *__restrict__ keys,
             }
             hi = s_end;
             if (hi > (uint32_t)FR) {
-                trail_pre = true;
                 // a big segment nobody listed (first run): record it; this run's
-                // output is discarded by the host
+                // output is discarded by the host.  The range stops before it:
+                // its unsorted keys would make rows the second run does not
+                // have, and the discarded rows could then outnumber the final ones
                 if (t == 0) {
                     const uint32_t slot = atomicAdd(n_big, 1u);
                     if (slot < big_cap) big[slot] = base + last;
                 }
-                hi = cnt;
+                hi = last;
             }
         }
     }
@@ -472,8 +476,10 @@ __global__ __launch_bounds__(FT) void segfin_kernel(uint64_t *__restrict__ keys,
             const uint32_t s0 = lead_pre ? 1u : 0u, s1 = nsegs - (trail_pre ? 1u : 0u);
             for (uint32_t j = s0 + (uint32_t)w; j < s1; j += FW) {
                 const uint32_t sa = seg_start(j), sb = seg_start(j + 1);
-                if (sb - sa < 2) {
-                    if (lane == 0) spk[sa] = sa;
+                if (sb - sa < 2 || low_bits == 0) {
+                    // nothing to sort (one key, or no low bits: the sort below
+                    // would run no pass and leave spk unwritten): identity positions
+                    for (uint32_t q = sa + (uint32_t)lane; q < sb; q += 64) spk[q] = q;
                     continue;
                 }
                 if (low_bits <= 22)
