@@ -900,12 +900,68 @@ int kman_mask_gram(kman_ctx *ctx, const uint64_t *d_masks, uint64_t n, uint32_t 
  *   = first_id + u in decimal, the sequence on one line.  seq, off (n + 1
  *   words) and kc are host copies of kman_unitig_spell's outputs.  The
  *   kman_format_* contract: *used is the size, KMAN_ECAP when cap is short or
- *   out is NULL; n == 0 writes nothing. */
+ *   out is NULL; n == 0 writes nothing.
+ *
+ * Edges between unitigs (`kmer unitigs --gfa`).  Unitig u has the text T_u that
+ *   kman_unitig_spell writes.  Orientation "+" (o = 0) reads T_u, orientation
+ *   "-" (o = 1) reads revcomp(T_u).  END e = 2 u + o is the right end of the
+ *   oriented text.  There is an EDGE (u, o) -> (v, p) when, for a base b, the
+ *   k-mer suffix_{k-1}(oriented T_u) + b is the first k-mer of v's text in
+ *   orientation p.  Within an end the edges are ordered by b, A C G T, the base
+ *   that extends the oriented text; the ends are ordered by e.
+ *   In rows: the "+" end of u is (its last row, the side that row is left
+ *   through), the "-" end is (its first row, the side opposite the one it is
+ *   left through); such a side's neighbours are those of the definition above.
+ *   A neighbour (j, t) names v "+" when j is v's first row and t the side that
+ *   row is entered by, v "-" when j is v's last row and t the side it is left
+ *   through.  Exactly one of the two holds: a side with a neighbour it is not
+ *   linked to is never inside a unitig, the two ends of a cut cycle see each
+ *   other, and both sides of a row that neighbours itself are ends.
+ *   No edge occurs twice; with (u, o, v, p) the edge (v, !p, u, !o) is present
+ *   (an edge can be its own mirror); an end has at most 4 edges, E <= 8 U.
+ *
+ * kman_unitig_edges: d_tkeys, nt, k, the index of kman_table_index (d_index,
+ *   index_bits) and kman_graph_rank's three arrays; none is written.  Outputs
+ *   in CSR form, for *n_ends = 2 U ends and *n_edges = E edges:
+ *     d_eoff  2 U + 1 u64: the edges of end e are d_edge[d_eoff[e],
+ *             d_eoff[e + 1]); d_eoff[2 U] = E
+ *     d_edge  E u32: (v << 1) | p
+ *   Both NULL: only *n_ends and *n_edges are set (the sizing call; it runs the
+ *   lookups too, so a caller that can afford the bound edge_cap = 4 * 2 U makes
+ *   one filling call instead).  Else d_eoff holds end_cap + 1 words and d_edge
+ *   edge_cap; a capacity below 2 U or E is KMAN_ECAP with both numbers set and
+ *   nothing written.  One output NULL, k even or outside 3..31, index_bits
+ *   outside 1..min(2k, KMAN_SCREEN_MAX_INDEX_BITS), nt >= KMAN_GRAPH_MAX_ROWS, a
+ *   NULL input with nt > 0: KMAN_EINVAL, nothing written.  nt == 0: both
+ *   numbers are 0 and d_eoff[0] = 0 when d_eoff is given.
+ *   Four passes: kman_unitig_spell's tile pass gives every first row its
+ *   unitig's ordinal; one thread per row notes the two ends' (row, side); one
+ *   thread per end, in tiles of KMAN_EDGE_TILE ends, looks its 4 extensions up
+ *   with the 4 searches advancing in lockstep (once per filling call), maps
+ *   every hit through d_start, d_pos and the ordinals to (v << 1) | p, keeps
+ *   the up to 4 words and takes its offset from a block scan and a decoupled
+ *   look-back over the tiles; a last pass compacts the words into d_edge.  No
+ *   atomics: two calls give equal bytes.  An index or rank arrays that do not
+ *   belong to the table give wrong edges, never a wild address or an endless
+ *   loop (every row, start, ordinal and offset read from memory is compared
+ *   with its array's size; every search runs a step count fixed before it
+ *   starts).  56 U bytes of the context's scratch and 4 nt of its second
+ *   scratch.  Launches are timed under "unitig_edges".  Synchronises.
+ *
+ * kman_format_gfa_segments (host): "S\tID\tSEQ\tLN:i:BASES\tKC:i:SUM\n" per
+ *   unitig, the arguments of kman_format_unitigs.
+ * kman_format_gfa_links (host): "L\tU\t+|-\tV\t+|-\t(k-1)M\n" per edge of the
+ *   n_units unitigs from first_id on, in CSR order.  eoff points at the first
+ *   of the slice's 2 n_units + 1 offsets, whose values are absolute and read
+ *   relative to eoff[0]; edge points at the slice's first edge.  V is the
+ *   word's unitig as it stands (an absolute ID).  Offsets that descend, k even
+ *   or outside 3..31: KMAN_EINVAL.  Both under the kman_format_* contract. */
 #define KMAN_GRAPH_R 0
 #define KMAN_GRAPH_L 1
 #define KMAN_GRAPH_NONE 0xFFFFFFFFu
 #define KMAN_GRAPH_MAX_ROWS (1ull << 31)
 #define KMAN_UNITIG_TILE 2048
+#define KMAN_EDGE_TILE 256
 int kman_graph_links(kman_ctx *ctx, const uint64_t *d_tkeys, uint64_t nt, uint32_t k, const uint64_t *d_index,
                      uint32_t index_bits, uint32_t *d_link);
 int kman_graph_rank(kman_ctx *ctx, const uint32_t *d_link, uint64_t nt, uint32_t *d_start, uint32_t *d_pos,
@@ -916,6 +972,14 @@ int kman_unitig_spell(kman_ctx *ctx, const uint64_t *d_tkeys, const void *d_tcou
                       uint64_t seq_cap, uint64_t *n_unitigs, uint64_t *n_bases);
 int kman_format_unitigs(const uint8_t *seq, const uint64_t *off, const uint64_t *kc, uint64_t n, uint64_t first_id,
                         char *out, size_t cap, size_t *used, int threads);
+int kman_unitig_edges(kman_ctx *ctx, const uint64_t *d_tkeys, uint64_t nt, uint32_t k, const uint64_t *d_index,
+                      uint32_t index_bits, const uint32_t *d_start, const uint32_t *d_pos, const uint32_t *d_nodes,
+                      uint64_t *d_eoff, uint64_t end_cap, uint32_t *d_edge, uint64_t edge_cap, uint64_t *n_ends,
+                      uint64_t *n_edges);
+int kman_format_gfa_segments(const uint8_t *seq, const uint64_t *off, const uint64_t *kc, uint64_t n,
+                             uint64_t first_id, char *out, size_t cap, size_t *used, int threads);
+int kman_format_gfa_links(const uint64_t *eoff, const uint32_t *edge, uint64_t n_units, uint64_t first_id, uint32_t k,
+                          char *out, size_t cap, size_t *used, int threads);
 
 /* ------------------------------------------- per-record order statistic
  * Not in the reference: one quantile (the median, by default) of the table

@@ -71,6 +71,7 @@ KMAN_GRAPH_L = 1  # and the left end; a (row, side) pair is packed as (row << 1)
 KMAN_GRAPH_NONE = 0xFFFFFFFF  # no partner
 KMAN_GRAPH_MAX_ROWS = 1 << 31  # tables of this many rows are refused (the packed u32 words)
 KMAN_UNITIG_TILE = 2048  # rows per tile of kman_unitig_spell's layout pass
+KMAN_EDGE_TILE = 256  # ends per tile of kman_unitig_edges' lookup pass
 KMAN_MATCH_RIGHT = 0
 KMAN_MATCH_LEFT = 1
 KMAN_MATCH_MIN = 2
@@ -265,6 +266,16 @@ SIGNATURES = {
     ),
     "kman_format_unitigs": (
         c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_size_t, POINTER(c_size_t), c_int],
+    ),
+    "kman_unitig_edges": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                c_uint64, c_void_p, c_uint64, POINTER(c_uint64), POINTER(c_uint64)],
+    ),
+    "kman_format_gfa_segments": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_size_t, POINTER(c_size_t), c_int],
+    ),
+    "kman_format_gfa_links": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint32, c_void_p, c_size_t, POINTER(c_size_t), c_int],
     ),
     "kman_format_classify": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_char_p, c_void_p,

@@ -570,6 +570,71 @@ extern "C" int kman_format_unitigs(const uint8_t *seq, const uint64_t *off, cons
     return run_sliced(n, out, cap, used, threads, size_of, write_at);
 }
 
+// "S\t%d\t%s\tLN:i:%d\tKC:i:%d\n" % (first_id + u, seq, bases, kc) per unitig (`kmer unitigs --gfa`)
+extern "C" int kman_format_gfa_segments(const uint8_t *seq, const uint64_t *off, const uint64_t *kc, uint64_t n,
+                                        uint64_t first_id, char *out, size_t cap, size_t *used, int threads) {
+    if (!used || (n && (!seq || !off || !kc))) return KMAN_EINVAL;
+    for (uint64_t u = 0; u < n; u++)
+        if (off[u + 1] < off[u]) return KMAN_EINVAL;
+    auto size_of = [&](uint64_t u) -> size_t {
+        const uint64_t len = off[u + 1] - off[u];
+        return 2 + ndigits(first_id + u) + 1 + len + 6 + ndigits(len) + 6 + ndigits(kc[u]) + 1;
+    };
+    auto write_at = [&](uint64_t u, char *p) -> char * {
+        const uint64_t len = off[u + 1] - off[u];
+        *p++ = 'S';
+        *p++ = '\t';
+        p = put_u64(p, first_id + u);
+        *p++ = '\t';
+        if (len) memcpy(p, seq + off[u], len);
+        p += len;
+        memcpy(p, "\tLN:i:", 6);
+        p = put_u64(p + 6, len);
+        memcpy(p, "\tKC:i:", 6);
+        p = put_u64(p + 6, kc[u]);
+        *p++ = '\n';
+        return p;
+    };
+    return run_sliced(n, out, cap, used, threads, size_of, write_at);
+}
+
+// "L\t%d\t%c\t%d\t%c\t%dM\n" % (first_id + u, "+-"[o], v, "+-"[p], k - 1) per edge, one item per end: end e of the
+// slice has the edges edge[eoff[e] - eoff[0], eoff[e + 1] - eoff[0]), words (v << 1) | p
+extern "C" int kman_format_gfa_links(const uint64_t *eoff, const uint32_t *edge, uint64_t n_units, uint64_t first_id,
+                                     uint32_t k, char *out, size_t cap, size_t *used, int threads) {
+    if (!used || (n_units && !eoff) || k < 3 || k > 31 || (k & 1u) == 0) return KMAN_EINVAL;
+    const uint64_t n_ends = 2 * n_units;
+    for (uint64_t e = 0; e < n_ends; e++)
+        if (eoff[e + 1] < eoff[e]) return KMAN_EINVAL;
+    if (n_ends && eoff[n_ends] > eoff[0] && !edge) return KMAN_EINVAL;
+    const size_t fixed = 2 + 1 + 1 + 1 + 1 + 1 + 1 + ndigits(k - 1) + 2;  // all but the two numbers
+    auto size_of = [&](uint64_t e) -> size_t {
+        const size_t du = ndigits(first_id + (e >> 1));
+        size_t s = 0;
+        for (uint64_t i = eoff[e] - eoff[0]; i < eoff[e + 1] - eoff[0]; i++) s += fixed + du + ndigits(edge[i] >> 1);
+        return s;
+    };
+    auto write_at = [&](uint64_t e, char *p) -> char * {
+        for (uint64_t i = eoff[e] - eoff[0]; i < eoff[e + 1] - eoff[0]; i++) {
+            *p++ = 'L';
+            *p++ = '\t';
+            p = put_u64(p, first_id + (e >> 1));
+            *p++ = '\t';
+            *p++ = (e & 1) ? '-' : '+';
+            *p++ = '\t';
+            p = put_u64(p, edge[i] >> 1);
+            *p++ = '\t';
+            *p++ = (edge[i] & 1u) ? '-' : '+';
+            *p++ = '\t';
+            p = put_u64(p, k - 1);
+            *p++ = 'M';
+            *p++ = '\n';
+        }
+        return p;
+    };
+    return run_sliced(n_ends, out, cap, used, threads, size_of, write_at);
+}
+
 // k in 33..64: keys as (hi, lo) word pairs (kman_extract_wide)
 extern "C" int kman_format_count_wide(const uint64_t *hi, const uint64_t *lo, const void *counts, uint32_t count_bytes,
                                       uint64_t n, uint32_t k, char *out, size_t cap, size_t *used, int threads) {

@@ -40,6 +40,19 @@
 //            every row adds its count to its unitig's KC with one 64-bit
 //            integer atomic (integer adds commute: two calls, equal bytes).
 //
+// kman_unitig_edges, four kernels:
+//   layout   the spelling's tile pass without its base sums (BASES = false):
+//            every head gets its ordinal.
+//   ends     one thread per row: a head notes (row, side opposite its exit) as
+//            its unitig's "-" end, a last row (pos >> 1 == nodes[start] - 1)
+//            (row, exit side) as the "+" end.
+//   edges    one thread per END, tiles of ETILE: the 4 extensions of the end's
+//            oriented k-mer are looked up in lockstep (row_lookup<4>), each hit
+//            (j, t) becomes (ord[start[j]] << 1) | p, "+" when j is a head
+//            entered at t; the up to 4 words and the end's offset (block scan,
+//            decoupled look-back) go to scratch.
+//   write    offsets and words into the outputs, once the capacities hold.
+//
 // Bounds, not values: every index read from memory (index pair, link, pointer,
 // start row, ordinal, offset) is compared with its array's size before it is
 // used, every search runs a step count fixed before it starts and every round
@@ -50,6 +63,10 @@
 // 8 (floor(log2 bucket) + 1) random key reads, 8 + 24 B of link words; a rank
 // round 2 x (12 B read + 12 B random read + 12 B written); spell 24 B read,
 // two dependent random reads (ordinal, offset), one byte and one atomic.
+// Edges, per row: 4 B in the layout, 12 B and one random ordinal in ends; per
+// END: 4 B end word, 8 B key, 4 index pairs, at most 4 (floor(log2 bucket) +
+// 1) random key reads, per hit three dependent random words (start, pos,
+// ordinal), 24 B of scratch written and read again, 8 B + 4 B per edge out.
 #include "common.h"
 #include "screen_lookup.h"
 
@@ -59,7 +76,9 @@ constexpr int UT = 256;
 constexpr int UR = 8;  // consecutive rows per thread of the layout kernel
 constexpr int UTILE = UT * UR;
 constexpr uint32_t NONE = KMAN_GRAPH_NONE;
+constexpr int ETILE = UT;  // ends per tile of the edges kernel, one per thread
 static_assert(UTILE == KMAN_UNITIG_TILE, "include/kman.h states the tile size");
+static_assert(ETILE == KMAN_EDGE_TILE, "include/kman.h states the tile size");
 static_assert(KMAN_GRAPH_R == 0 && KMAN_GRAPH_L == 1, "a state's opposite side is its word ^ 1");
 
 // the reverse complement of a 2k-bit key
@@ -249,6 +268,8 @@ __global__ __launch_bounds__(UT) void rank_finish_kernel(const uint64_t *__restr
 }
 
 // ---------------------------------------------------------------- spell
+// BASES false: the ordinals alone, for kman_unitig_edges (nodes and hoff are not touched, one look-back)
+template <bool BASES>
 __global__ __launch_bounds__(UT) void layout_kernel(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ nodes,
                                                     uint32_t nt, uint32_t k, uint32_t *__restrict__ ord,
                                                     uint64_t *__restrict__ hoff, uint64_t *status, uint64_t n_tiles,
@@ -265,17 +286,17 @@ __global__ __launch_bounds__(UT) void layout_kernel(const uint32_t *__restrict__
     for (int r = 0; r < UR; r++) {
         const uint64_t i = r0 + r;
         const bool head = i < nt && (pos[i < nt ? i : 0] >> 1) == 0;
-        nn[r] = head ? nodes[i] : 0u;
+        nn[r] = BASES && head ? nodes[i] : 0u;
         heads |= (uint32_t)head << r;
         bases += head ? (uint64_t)nn[r] + (k - 1) : 0ull;
     }
     uint32_t tc = 0;
     uint64_t tb = 0;
     uint32_t c = block_exclusive_scan<UT>((uint32_t)__popc(heads), SumU32(), 0u, lds_c, &tc);
-    uint64_t b = block_exclusive_scan<UT>(bases, SumU64(), (uint64_t)0, lds_b, &tb);
+    uint64_t b = BASES ? block_exclusive_scan<UT>(bases, SumU64(), (uint64_t)0, lds_b, &tb) : 0ull;
     if ((threadIdx.x >> 6) == 0) {
         const uint64_t bc = wave_lookback<0>(status, tile, (uint64_t)tc, epoch, err);
-        const uint64_t bb = wave_lookback<0>(status + n_tiles, tile, tb, epoch, err);
+        const uint64_t bb = BASES ? wave_lookback<0>(status + n_tiles, tile, tb, epoch, err) : 0ull;
         if (lane_id() == 0) {
             lds_base[0] = bc;
             lds_base[1] = bb;
@@ -291,7 +312,7 @@ __global__ __launch_bounds__(UT) void layout_kernel(const uint32_t *__restrict__
         const bool head = (heads >> r) & 1u;
         ord[i] = head ? c : NONE;
         if (head) {
-            hoff[i] = b;
+            if (BASES) hoff[i] = b;
             c++;
             b += (uint64_t)nn[r] + (k - 1);
         }
@@ -328,6 +349,104 @@ __global__ __launch_bounds__(UT) void spell_kernel(const uint64_t *__restrict__ 
         if (w < total) seq[w] = (uint8_t)(B >> (8 * (s & 3u)));
     }
     atomicAdd(&kc[o], (unsigned long long)tcounts[i]);
+}
+
+// ---------------------------------------------------------------- edges
+// endw[2 u + o] = (row << 1) | side of end o of unitig u: the last row and the
+// side it is left through ("+"), the first row and the opposite side ("-")
+__global__ __launch_bounds__(UT) void ends_kernel(const uint32_t *__restrict__ start, const uint32_t *__restrict__ pos,
+                                                  const uint32_t *__restrict__ nodes, const uint32_t *__restrict__ ord,
+                                                  uint32_t nt, uint64_t nu, uint32_t *__restrict__ endw) {
+    const uint32_t i = blockIdx.x * UT + threadIdx.x;
+    if (i >= nt) return;
+    const uint32_t a = start[i];
+    if (a >= nt) return;
+    const uint32_t u = ord[a];
+    if ((uint64_t)u >= nu) return;  // (NONE: the start is no head)
+    const uint32_t pw = pos[i], p = pw >> 1, o = pw & 1u;
+    if (p == 0) endw[2 * (uint64_t)u + 1] = (i << 1) | (o ^ 1u);
+    if (p + 1 == nodes[a]) endw[2 * (uint64_t)u] = (i << 1) | o;  // (p < 2^31)
+}
+
+// One thread per end, tiles of ETILE ends: the 4 keys that extend the end's
+// oriented k-mer are looked up in lockstep, each hit (j, t) is resolved to
+// (v << 1) | p through start, pos and ord, the up to 4 words go to ew[e] and
+// the end's offset, from a block scan and a look-back over the tiles, to
+// eoff[e].
+__global__ __launch_bounds__(UT) void edges_kernel(const uint64_t *__restrict__ tkeys, uint32_t nt, uint32_t k,
+                                                   const uint64_t *__restrict__ index, uint32_t shift,
+                                                   const uint32_t *__restrict__ start, const uint32_t *__restrict__ pos,
+                                                   const uint32_t *__restrict__ ord,
+                                                   const uint32_t *__restrict__ endw, uint64_t n_ends,
+                                                   uint4 *__restrict__ ew, uint64_t *__restrict__ eoff,
+                                                   uint64_t *status, uint32_t *counter, uint32_t epoch, uint32_t *err) {
+    __shared__ uint32_t lds_c[UT / 64];
+    __shared__ uint64_t lds_base;
+    __shared__ uint32_t lds_tile;
+    const int64_t tile = grab_tile(counter, &lds_tile);
+    const uint64_t e = (uint64_t)tile * ETILE + threadIdx.x;
+    const uint32_t me = e < n_ends ? endw[e] : NONE;
+    uint32_t w[4] = {NONE, NONE, NONE, NONE}, c = 0;
+    if ((me >> 1) < nt) {  // (NONE >> 1 = 2^31 - 1 >= nt)
+        const uint64_t mask = (1ull << (2 * k)) - 1;  // (k <= 31)
+        const uint64_t x = tkeys[me >> 1] & mask;
+        const uint64_t z = (me & 1u) == KMAN_GRAPH_R ? x : rc_key(x, k);  // the k-mer as the end's orientation reads it
+        uint64_t kf[4], row[4];
+        uint32_t fwd = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint64_t y = ((z << 2) | (uint64_t)j) & mask;
+            const uint64_t r = rc_key(y, k);
+            kf[j] = y < r ? y : r;
+            fwd |= (uint32_t)(y < r) << j;
+        }
+        const uint32_t hit = row_lookup<4>(kf, shift, index, tkeys, (uint64_t)nt, row);
+        const uint64_t nu = n_ends >> 1;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (!((hit >> j) & 1u)) continue;
+            const uint32_t rj = (uint32_t)row[j];  // (< nt)
+            // a forward neighbour is entered at its L, a reversed one at its R
+            const uint32_t t = ((fwd >> j) & 1u) ? KMAN_GRAPH_L : KMAN_GRAPH_R;
+            const uint32_t a = start[rj], pw = pos[rj];
+            const uint32_t v = a < nt ? ord[a] : NONE;
+            if ((uint64_t)v >= nu) continue;
+            // v "+": entered at its first row's entry side; else at its last row's exit side, v "-"
+            const bool plus = (pw >> 1) == 0 && t == ((pw & 1u) ^ 1u);
+            const uint32_t word = (v << 1) | (plus ? 0u : 1u);  // (v < nu <= nt < 2^31)
+#pragma unroll
+            for (int q = 0; q < 4; q++) w[q] = q == (int)c ? word : w[q];  // (no indexed register array)
+            c++;
+        }
+    }
+    uint32_t tc = 0;
+    const uint32_t ex = block_exclusive_scan<UT>(c, SumU32(), 0u, lds_c, &tc);
+    if ((threadIdx.x >> 6) == 0) {
+        const uint64_t base = wave_lookback<0>(status, tile, (uint64_t)tc, epoch, err);
+        if (lane_id() == 0) lds_base = base;
+    }
+    __syncthreads();
+    if (e < n_ends) {
+        eoff[e] = lds_base + ex;
+        ew[e] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+__global__ __launch_bounds__(UT) void edges_write_kernel(const uint4 *__restrict__ ew, const uint64_t *__restrict__ eoff,
+                                                         uint64_t n_ends, uint64_t total,
+                                                         uint64_t *__restrict__ d_eoff, uint32_t *__restrict__ d_edge) {
+    const uint64_t e = (uint64_t)blockIdx.x * UT + threadIdx.x;
+    if (e >= n_ends) return;
+    if (e == 0) d_eoff[n_ends] = total;
+    const uint64_t a = smin64(eoff[e], total);
+    const uint64_t b = smin64(e + 1 < n_ends ? eoff[e + 1] : total, total);
+    d_eoff[e] = a;
+    const uint64_t c = b > a ? smin64(b - a, 4) : 0;  // (a + c <= b <= total)
+    const uint4 w = ew[e];
+    if (c > 0) d_edge[a] = w.x;
+    if (c > 1) d_edge[a + 1] = w.y;
+    if (c > 2) d_edge[a + 2] = w.z;
+    if (c > 3) d_edge[a + 3] = w.w;
 }
 
 inline uint32_t blocks_of(uint64_t n) { return (uint32_t)ceil_div(n, UT); }
@@ -462,7 +581,7 @@ extern "C" int kman_unitig_spell(kman_ctx *ctx, const uint64_t *d_tkeys, const v
         KTimer kt_(ctx, "unitig_spell");
         uint32_t epoch, *counter;
         KMAN_TRY(kman_lookback_begin(ctx, 2 * T, &epoch, &counter));
-        hipLaunchKernelGGL(layout_kernel, dim3((uint32_t)T), dim3(UT), 0, ctx->stream, d_pos, d_nodes, (uint32_t)nt, k,
+        hipLaunchKernelGGL(layout_kernel<true>, dim3((uint32_t)T), dim3(UT), 0, ctx->stream, d_pos, d_nodes, (uint32_t)nt, k,
                            ord, hoff, ctx->d_status, T, counter, epoch, ctx->d_err);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -487,6 +606,95 @@ extern "C" int kman_unitig_spell(kman_ctx *ctx, const uint64_t *d_tkeys, const v
                                (const uint64_t *)d_tcounts, (uint32_t)nt, k, d_start, d_pos, d_nodes, ord, hoff, nu,
                                total, d_off, d_unodes, (unsigned long long *)d_kc, d_seq);
         HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KMAN_OK;
+}
+
+extern "C" int kman_unitig_edges(kman_ctx *ctx, const uint64_t *d_tkeys, uint64_t nt, uint32_t k,
+                                 const uint64_t *d_index, uint32_t index_bits, const uint32_t *d_start,
+                                 const uint32_t *d_pos, const uint32_t *d_nodes, uint64_t *d_eoff, uint64_t end_cap,
+                                 uint32_t *d_edge, uint64_t edge_cap, uint64_t *n_ends, uint64_t *n_edges) {
+    if (!ctx || !n_ends || !n_edges) return KMAN_EINVAL;
+    if (k < 3 || k > 31 || (k & 1u) == 0)
+        return kman_fail(ctx, KMAN_EINVAL, "kman_unitig_edges: k must be odd and in [3, 31], got %u", k);
+    if (!index_bits_ok(k, index_bits))
+        return kman_fail(ctx, KMAN_EINVAL, "index_bits must be in [1, min(2k, %d)], got %u (k = %u)",
+                         KMAN_SCREEN_MAX_INDEX_BITS, index_bits, k);
+    KMAN_TRY(graph_args(ctx, "kman_unitig_edges", nt));
+    const bool count_only = !d_eoff && !d_edge;
+    if (!count_only && (!d_eoff || !d_edge))
+        return kman_fail(ctx, KMAN_EINVAL, "kman_unitig_edges: the two outputs go together (both, or none to count)");
+    if (nt > 0 && (!d_tkeys || !d_index || !d_start || !d_pos || !d_nodes))
+        return kman_fail(ctx, KMAN_EINVAL, "kman_unitig_edges: null buffer");
+    *n_ends = *n_edges = 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (nt == 0) {
+        if (d_eoff) {
+            HIP_TRY(ctx, hipMemsetAsync(d_eoff, 0, 8, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return KMAN_OK;
+    }
+    // the heads' ordinals live in the second scratch: the first one is sized once the ends are counted
+    void *aux = nullptr;
+    KMAN_TRY(kman_aux(ctx, (size_t)4 * nt, &aux));
+    uint32_t *ord = (uint32_t *)aux;
+    const uint64_t T = ceil_div(nt, UTILE);
+    uint64_t nu = 0, ne = 0, total = 0;
+    {
+        KTimer kt_(ctx, "unitig_edges");
+        uint32_t epoch, *counter;
+        KMAN_TRY(kman_lookback_begin(ctx, T, &epoch, &counter));
+        hipLaunchKernelGGL(layout_kernel<false>, dim3((uint32_t)T), dim3(UT), 0, ctx->stream, d_pos,
+                           (const uint32_t *)nullptr, (uint32_t)nt, k, ord, (uint64_t *)nullptr, ctx->d_status, T,
+                           counter, epoch, ctx->d_err);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    KMAN_TRY(kman_lookback_total(ctx, T, &nu));
+    if (nu > nt) return kman_fail(ctx, KMAN_EHIP, "kman_unitig_edges: %llu heads in %llu rows", (unsigned long long)nu,
+                                  (unsigned long long)nt);
+    ne = 2 * nu;
+    uint4 *ew = nullptr;
+    uint64_t *eoff = nullptr;
+    if (ne) {
+        void *scr = nullptr;
+        KMAN_TRY(kman_scratch(ctx, (size_t)28 * ne, &scr));
+        ew = (uint4 *)scr;
+        eoff = (uint64_t *)(ew + ne);
+        uint32_t *endw = (uint32_t *)(eoff + ne);
+        const uint64_t T2 = ceil_div(ne, ETILE);
+        {
+            KTimer kt_(ctx, "unitig_edges");
+            HIP_TRY(ctx, hipMemsetAsync(endw, 0xFF, (size_t)4 * ne, ctx->stream));
+            hipLaunchKernelGGL(ends_kernel, dim3(blocks_of(nt)), dim3(UT), 0, ctx->stream, d_start, d_pos, d_nodes, ord,
+                               (uint32_t)nt, nu, endw);
+            HIP_TRY(ctx, hipGetLastError());
+            uint32_t epoch, *counter;
+            KMAN_TRY(kman_lookback_begin(ctx, T2, &epoch, &counter));
+            hipLaunchKernelGGL(edges_kernel, dim3((uint32_t)T2), dim3(UT), 0, ctx->stream, d_tkeys, (uint32_t)nt, k,
+                               d_index, 2 * k - index_bits, d_start, d_pos, ord, endw, ne, ew, eoff, ctx->d_status,
+                               counter, epoch, ctx->d_err);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        KMAN_TRY(kman_lookback_total(ctx, T2, &total));
+    }
+    *n_ends = ne;
+    *n_edges = total;
+    if (count_only) return KMAN_OK;
+    if (ne > end_cap || total > edge_cap)
+        return kman_fail(ctx, KMAN_ECAP, "kman_unitig_edges: %llu ends with %llu edges for capacities %llu and %llu",
+                         (unsigned long long)ne, (unsigned long long)total, (unsigned long long)end_cap,
+                         (unsigned long long)edge_cap);
+    {
+        KTimer kt_(ctx, "unitig_edges");
+        if (ne) {
+            hipLaunchKernelGGL(edges_write_kernel, dim3(blocks_of(ne)), dim3(UT), 0, ctx->stream, ew, eoff, ne, total,
+                               d_eoff, d_edge);
+            HIP_TRY(ctx, hipGetLastError());
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(d_eoff, 0, 8, ctx->stream));
+        }
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KMAN_OK;

@@ -340,6 +340,13 @@ def hpc():
                              "no run crosses a record")
 
 
+def gfa():
+    return click.option("--gfa", "gfa", is_flag=True,
+                        help="Write the graph, not the nodes alone: GFA 1.0, a header line, one "
+                             "\"S ID SEQ LN:i:BASES KC:i:SUM\" line per unitig and one \"L U +|- V +|- (K-1)M\" line per "
+                             "edge between two unitig ends (tab-separated), the edges found on the GPU")
+
+
 def compare_inputs():
     return click.argument("inputs", metavar="INPUT INPUT [INPUT ...]", nargs=-1,
                           type=click.Path(exists=True, file_okay=True, dir_okay=False, readable=True))

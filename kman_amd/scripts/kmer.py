@@ -1137,8 +1137,17 @@ K is odd and in 3..31.  -L / -U select the k-mers that become nodes (-L 2
 drops the k-mers a read set holds once, and with them the tips and bubbles of
 sequencing errors).  An INPUT without k-mers writes an empty OUTPUT; OUTPUT is
 never compressed.
-Out of scope: GFA links between unitigs, colours, K > 31, and tables larger
-than one GPU.
+
+--gfa writes GFA 1.0 instead: the unitigs as S lines and, as L lines with a
+K-1 base overlap, every edge between two unitig ends: U + or - (the unitig's
+text or its reverse complement) is followed by V + or - when its last K-1
+bases and one more base give V's first k-mer.  The ends' extensions are looked
+up in the table on the GPU (kman_unitig_edges); every edge is written from
+both sides, an edge that is its own mirror once.  An INPUT without k-mers
+then writes the header line alone.
+
+Out of scope: colours, K > 31, and tables larger than one GPU.
+
 Launched one process per GPU, the command runs on rank 0 alone.
 """)
 @args.input_path()
@@ -1151,9 +1160,10 @@ Launched one process per GPU, the command runs on rank 0 alone.
 @args.unitig_max_count()
 @args.index_bits()
 @args.hpc()
+@args.gfa()
 def unitigs(input_path: str, output_path: str, k: int, input_format: str = "auto", min_qual: int = 0,
             phred_offset: str = "33", min_count: int = 1, max_count: Optional[int] = None,
-            index_bits: Optional[int] = None, hpc: bool = False) -> None:
+            index_bits: Optional[int] = None, hpc: bool = False, gfa: bool = False) -> None:
     input_file_exists(input_path)
     fastq = _is_fastq(input_path, input_format)
     _check_unitig_options(k, output_path, input_path, min_qual, fastq, min_count, max_count, index_bits)
@@ -1175,11 +1185,15 @@ def unitigs(input_path: str, output_path: str, k: int, input_format: str = "auto
             ranged = engine.filtered_copy(dev, table, min_count, max_count)
             engine.free_result(table)
             table = ranged
-        res = engine.unitigs(dev, table, index_bits=index_bits)
+        res = engine.unitigs(dev, table, index_bits=index_bits, links=True) if gfa else \
+            engine.unitigs(dev, table, index_bits=index_bits)
     finally:
         engine.free_result(table)
     with open(output_path, "wb") as fh:
-        engine.emit_unitigs(res, fh)
+        if gfa:
+            engine.emit_gfa(res, fh)
+        else:
+            engine.emit_unitigs(res, fh)
     logging.info("That's all!")
 
 
