@@ -13,11 +13,10 @@
 //              colour only when no other reference holds its k-mer).  After
 //              this a window counts for colour c when bit c is set, in both
 //              modes.
-//   records    as in screen.hip: thread 0 cuts the slice of d_rec_seq that owns
-//              the tile's bases; <= CCAP entries are staged in LDS (slot =
-//              record - first record of the slice, one round), more are
-//              searched in global memory (slot = the offset of the record's
-//              first base in the tile, CTILE / CCAP rounds of CCAP offsets).
+//   records    as in screen.hip (tile_records.h: cut_slice, stage_slice,
+//              owner_walk): <= CCAP slice entries are staged in LDS (one round
+//              of slots), more are searched in global memory (CTILE / CCAP
+//              rounds of CCAP slots).
 //   colours    in chunks of CCH = 8: a chunk holds 8 register counters per run
 //              of one record and 8 x CCAP u32 LDS slots.  n_colors <= 8 is one
 //              chunk (the MULTI = 0 instances have no chunk loop); 64 colours
@@ -32,9 +31,9 @@
 //              (slot, plane) is one u32 atomicAdd to d_out.  Integer adds
 //              commute: the result does not depend on the order.
 //
-// Bounds, not values: everything screen.hip states (lo <= hi <= nt clamped,
-// key and mask indices < nt, record indices inside the slice, slots < CCAP);
-// the plane index of every global add is 1 + c0 + cc with c0 + cc < n_colors
+// Bounds, not values: tile_records.h for the records and slots, screen_lookup.h
+// for the table; every record that addresses d_out is checked against
+// n_records, and the plane index of every global add is 1 + c0 + cc with c0 + cc < n_colors
 // checked where it is formed.
 //
 // kman_classify_pick: one thread per record reads its n_colors hit words
@@ -48,6 +47,7 @@
 #include "common.h"
 #include "kmer.h"
 #include "screen_lookup.h"
+#include "tile_records.h"
 
 namespace {
 
@@ -62,21 +62,6 @@ static_assert(KMAN_CLASSIFY_MAX_COLORS == 64, "a mask is one u64");
 static_assert(KMAN_CLASSIFY_MAX_COLORS % CCH == 0, "whole chunks");
 static_assert((KMAN_CLASSIFY_SPECIFIC & (KMAN_CLASSIFY_SPECIFIC - 1)) == 0 && KMAN_CLASSIFY_SPECIFIC != KMAN_CANONICAL,
               "one flag bit of its own");
-
-// the number of entries of rs[0, n) that are <= b
-KMAN_DEV uint64_t upper_count(const uint64_t *rs, uint64_t n, uint64_t b) {
-    uint64_t lo = 0, len = n;
-    for (int s = 0; s < 64 && len; s++) {
-        const uint64_t half = len >> 1;
-        if (rs[lo + half] <= b) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
-}
 
 template <int CANON, int SPEC, int MULTI>
 __global__ __launch_bounds__(CT) void classify_kernel(const uint8_t *__restrict__ codes, uint64_t n_bases, int k,
@@ -94,20 +79,17 @@ __global__ __launch_bounds__(CT) void classify_kernel(const uint8_t *__restrict_
 
     const uint64_t tb = (uint64_t)blockIdx.x * CTILE;
     if (threadIdx.x == 0) {
-        const uint64_t last = smin64(tb + CTILE, n_bases) - 1;
-        const uint64_t u0 = upper_count(rec_seq, n_records, tb), u1 = upper_count(rec_seq, n_records, last);
-        const uint64_t r0 = u0 ? u0 - 1 : 0;
-        s_r0 = r0;
-        s_ns = u1 > r0 ? u1 - r0 : 0;
+        const TileSlice s = cut_slice(rec_seq, n_records, tb, umin64(tb + CTILE, n_bases) - 1);
+        s_r0 = s.r0;
+        s_ns = s.ns;
         s_any = 0;
     }
     stage_codes<CT, CEI>(codes, n_bases, tb, scodes);
     __syncthreads();
     const uint64_t r0 = s_r0, ns = s_ns;
     if (ns == 0) return;  // (no record starts at or before the tile's last base)
-    const bool big = ns > (uint64_t)CCAP;
-    if (!big)
-        for (uint32_t i = threadIdx.x; i < (uint32_t)ns; i += CT) srec[i] = rec_seq[r0 + i];
+    const SliceView sv = stage_slice<CT, CCAP>(rec_seq, {r0, ns, 0}, srec);
+    const bool big = sv.big;
 
     const uint64_t mask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
     uint64_t kf[CEI], kr[CEI];
@@ -129,7 +111,9 @@ __global__ __launch_bounds__(CT) void classify_kernel(const uint8_t *__restrict_
     if (MULTI && any) atomicOr(&s_any, (unsigned long long)any);
 
     // ---- per-record, per-colour reduction
-    const uint64_t *rs = big ? rec_seq + r0 : srec;
+    struct Run {
+        uint32_t h[CCH];
+    };
     const int rounds = big ? CTILE / CCAP : 1;
     const uint32_t nchunks = MULTI ? (n_colors + CCH - 1) / CCH : 1;
     for (int c = 0; c < rounds; c++) {
@@ -141,51 +125,22 @@ __global__ __launch_bounds__(CT) void classify_kernel(const uint8_t *__restrict_
             // (block-uniform: s_any is complete after the first barrier and is not written again)
             const bool chunk_on = ch == 0 || ((s_any >> c0) & 0xffull) != 0;
             const bool mine = ch == 0 || ((any >> c0) & 0xffull) != 0;
-            if (chunk_on && valid && mine) {
-                const uint64_t slot0 = (uint64_t)c * CCAP;
-                uint64_t u = 0, nxt = 0;  // u: slice entries <= the current base; nxt: the base where that changes
-                uint32_t w = 0, h[CCH];
-#pragma unroll
-                for (int cc = 0; cc < CCH; cc++) h[cc] = 0;
-                auto flush = [&]() {
-                    if (w == 0 || u == 0) return;  // (u == 0: bases before the first record)
-                    const uint64_t ri = u - 1;
-                    uint64_t key = ri;
-                    if (big) {
-                        const uint64_t st = rs[ri];
-                        key = st > tb ? st - tb : 0;
-                    }
-                    if (key >= slot0 && key - slot0 < (uint64_t)CCAP) {
-                        const uint32_t slot = (uint32_t)(key - slot0);
-                        if (ch == 0) atomicAdd(&sw[slot], w);
-#pragma unroll
-                        for (int cc = 0; cc < CCH; cc++)
-                            if (h[cc]) atomicAdd(&sc[cc * CCAP + slot], h[cc]);
-                        if (big) srec[slot] = r0 + ri;  // (every writer of a slot stores the same record)
-                    }
-                };
-#pragma unroll
-                for (int j = 0; j < CEI; j++) {
-                    const uint64_t b = p0 + j;
-                    if (j == 0 || b >= nxt) {
-                        flush();
-                        w = 0;
-#pragma unroll
-                        for (int cc = 0; cc < CCH; cc++) h[cc] = 0;
-                        u = upper_count(rs, ns, b);
-                        nxt = u < ns ? rs[u] : ~0ull;
-                    }
-                    if ((valid >> j) & 1u) {
-                        w++;
+            if (chunk_on && valid && mine)
+                owner_walk<CEI, CCAP, Run>(
+                    sv, r0, tb, p0, valid, c, srec,
+                    [&](Run &a, int j) {
                         const uint32_t bits = (uint32_t)(m[j] >> c0) & 0xffu;
                         if (bits) {
 #pragma unroll
-                            for (int cc = 0; cc < CCH; cc++) h[cc] += (bits >> cc) & 1u;
+                            for (int cc = 0; cc < CCH; cc++) a.h[cc] += (bits >> cc) & 1u;
                         }
-                    }
-                }
-                flush();
-            }
+                    },
+                    [&](const Run &a, uint32_t w, uint32_t slot) {
+                        if (ch == 0) atomicAdd(&sw[slot], w);
+#pragma unroll
+                        for (int cc = 0; cc < CCH; cc++)
+                            if (a.h[cc]) atomicAdd(&sc[cc * CCAP + slot], a.h[cc]);
+                    });
             __syncthreads();
             if (chunk_on) {
                 for (uint32_t i = threadIdx.x; i < (uint32_t)CCAP; i += CT) {

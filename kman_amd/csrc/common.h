@@ -302,6 +302,15 @@ struct SumU64 {
 struct SumU32 {
     KMAN_DEV uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
 };
+struct MaxU64 {
+    KMAN_DEV uint64_t operator()(uint64_t a, uint64_t b) const { return a > b ? a : b; }
+};
+struct MaxU32 {
+    KMAN_DEV uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
+};
+
+KMAN_DEV uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+KMAN_DEV uint64_t umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
 
 // ------------------------------------------------------ decoupled look-back
 // the wave's sum (OP 0) or max (OP 1) of v in every lane: DPP row shifts and
@@ -309,9 +318,6 @@ struct SumU32 {
 // butterfly through ds_bpermute took six, two per step for 64 bits)
 template <int OP>
 KMAN_DEV uint64_t wave_reduce_lb(uint64_t v) {
-    struct MaxU64 {
-        KMAN_DEV uint64_t operator()(uint64_t a, uint64_t b) const { return a > b ? a : b; }
-    };
     if (OP == 0) v = wave_inclusive_scan(v, SumU64(), (uint64_t)0);
     else v = wave_inclusive_scan(v, MaxU64(), (uint64_t)0);
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), 63) << 32) |

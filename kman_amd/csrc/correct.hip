@@ -16,7 +16,7 @@
 //   sites   kman_correct_sites, one block of 256 threads per tile of CTILE =
 //           4096 bases.  The tile's words and a halo of CHALO >= 33 go to LDS,
 //           with the word before the tile; thread 0 cuts the tile's slice of
-//           d_rec_seq (runs_kernel's: staged when <= CCAP entries, searched in
+//           d_rec_seq (tile_records.h: staged when <= CCAP entries, searched in
 //           global memory above).  A wave owns 1024 consecutive bases, 64 at a
 //           time, one per lane.  A lane whose base is weak finds its record
 //           (one search); it is a run's START when the base is the record's
@@ -46,8 +46,7 @@
 //           L bytes takes about L / 1024 steps of one wave; there is no
 //           block-per-record path for very long reads (cut.hip's limit).
 //
-// Bounds, not values: every record comes from a search over at most n_records
-// entries with a step count fixed before it starts; a record's bounds are
+// Bounds, not values: tile_records.h for the slice; a record's bounds are
 // clamped (s <= a < e <= n_bases) before they are used; a start reads LDS
 // words at most k past its own (< CTILE + CHALO); p < e, so d_fix is written
 // below n_bases; codes are read below n_bases + 64 (the parsers' padding); the
@@ -61,7 +60,9 @@
 // the halo), 1 B written per base (the fill); per site 64 B of codes, at most
 // 3 k lookups (screen.hip's bytes per lookup) and one byte stored.
 #include "common.h"
+#include "bytes16.h"
 #include "screen_lookup.h"
+#include "tile_records.h"
 
 namespace {
 
@@ -76,24 +77,8 @@ static_assert(CPW % 64 == 0, "a wave walks its bases 64 at a time");
 
 #define WC_NONE KMAN_WC_NONE
 
-KMAN_DEV uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 KMAN_DEV bool is_weak(uint32_t w, uint32_t c) { return w != WC_NONE && w < c; }
 KMAN_DEV bool is_solid(uint32_t w, uint32_t c) { return w != WC_NONE && w >= c; }
-
-// the number of entries of rs[0, n) that are <= b (screen.hip's)
-KMAN_DEV uint64_t upper_count(const uint64_t *rs, uint64_t n, uint64_t b) {
-    uint64_t lo = 0, len = n;
-    for (int s = 0; s < 64 && len; s++) {
-        const uint64_t half = len >> 1;
-        if (rs[lo + half] <= b) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
-}
 
 // bit i of the low 32 bits of x to bit 2 i
 KMAN_DEV uint64_t spread2(uint64_t x) {
@@ -134,13 +119,10 @@ __global__ __launch_bounds__(CT_) void correct_sites_kernel(
     const uint64_t tb = (uint64_t)blockIdx.x * CTILE;
     const uint64_t tend = umin64(tb + CTILE, n_bases);  // (tb < n_bases: the grid is ceil(n_bases / CTILE))
     if (threadIdx.x == 0) {
-        // the records that own bases [tb, tend) (runs_kernel's slice)
-        const uint64_t u0 = upper_count(rec_seq, n_records, tb), u1 = upper_count(rec_seq, n_records, tend - 1);
-        const uint64_t r0 = u0 ? u0 - 1 : 0;
-        const uint64_t ns = u1 > r0 ? u1 - r0 : 0;
-        s_r0 = r0;
-        s_ns = ns;
-        s_next = r0 + ns < n_records ? umin64(rec_seq[r0 + ns], n_bases) : n_bases;
+        const TileSlice s = cut_slice(rec_seq, n_records, tb, tend - 1, n_bases);  // the records that own [tb, tend)
+        s_r0 = s.r0;
+        s_ns = s.ns;
+        s_next = s.next;
         s_prev = tb ? wc[tb - 1] : WC_NONE;
     }
     // the tile's words and the halo (past n_bases: NONE, neither weak nor solid)
@@ -159,12 +141,9 @@ __global__ __launch_bounds__(CT_) void correct_sites_kernel(
     __syncthreads();
     const uint64_t r0 = s_r0, ns = s_ns, next = s_next;
     if (ns == 0) return;  // (no record starts at or before the tile's last base; block-uniform)
-    const bool big = ns > (uint64_t)CCAP;
-    if (!big) {
-        for (uint32_t i = threadIdx.x; i < (uint32_t)ns; i += CT_) srec[i] = rec_seq[r0 + i];
-        __syncthreads();  // (block-uniform)
-    }
-    const uint64_t *rs = big ? rec_seq + r0 : srec;
+    const SliceView sv = stage_slice<CT_, CCAP>(rec_seq, {r0, ns, next}, srec);
+    if (!sv.big) __syncthreads();  // (block-uniform)
+    const uint64_t *rs = sv.rs;
 
     const int lane = lane_id();
     const uint32_t wbase = (threadIdx.x >> 6) * (uint32_t)CPW;
@@ -184,7 +163,7 @@ __global__ __launch_bounds__(CT_) void correct_sites_kernel(
             const uint64_t u = upper_count(rs, ns, a);
             if (u != 0) {  // (0: a base before the first record)
                 const uint64_t s = umin64(rs[u - 1], a);
-                const uint64_t e = umin64(u < ns ? rs[u] : next, n_bases);
+                const uint64_t e = umin64(sv.ent(u), n_bases);
                 const uint32_t before = i ? sw[i - 1] : s_prev;
                 if (e > a && (a == s || !is_weak(before, min_count))) {
                     // b: the first window start after a that is not weak, or e; given up past a + k
@@ -276,28 +255,6 @@ __global__ __launch_bounds__(CT_) void apply_codes_kernel(uint8_t *__restrict__ 
     }
 }
 
-// the 16-byte word of v at p (p % 16 == 0); bytes at or past n read as `fill`
-KMAN_DEV uint4 load16(const uint8_t *__restrict__ v, uint64_t n, uint64_t p, uint32_t fill) {
-    if (p + 16 <= n) return *reinterpret_cast<const uint4 *>(v + p);
-    uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j >> 2] |= (p + j < n ? (uint32_t)v[p + j] : fill) << (8 * (j & 3));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-KMAN_DEV uint32_t byte_of(const uint4 &v, int j) {
-    const uint32_t w = (j >> 2) == 0 ? v.x : (j >> 2) == 1 ? v.y : (j >> 2) == 2 ? v.z : v.w;
-    return (w >> (8 * (j & 3))) & 0xffu;
-}
-
-// the first byte of the line after the terminator that starts at t (t >= b: none)
-KMAN_DEV uint64_t line_after(const uint8_t *text, uint64_t t, uint64_t b) {
-    if (t >= b) return b;
-    uint64_t n = t + 1;
-    if (text[t] == '\r' && n < b && text[n] == '\n') n++;
-    return n;
-}
-
 // one wave per record: d_nfix[r], and the text bytes of its fixed bases
 __global__ __launch_bounds__(CT_) void apply_records_kernel(const uint8_t *__restrict__ fix, uint64_t n_bases,
                                                             const uint64_t *__restrict__ rec_seq, uint64_t n_records,
@@ -314,7 +271,7 @@ __global__ __launch_bounds__(CT_) void apply_records_kernel(const uint8_t *__res
         const uint64_t p = base + 16ull * (uint32_t)lane;
         uint32_t n = 0;
         if (p < e) {
-            const uint4 f = load16(fix, n_bases, p, NOFIX);
+            const uint4 f = load16<NOFIX>(fix, n_bases, p);
 #pragma unroll
             for (int j = 0; j < 16; j++) n += (p + j >= s && p + j < e && byte_of(f, j) != NOFIX) ? 1u : 0u;
         }
@@ -332,7 +289,7 @@ __global__ __launch_bounds__(CT_) void apply_records_kernel(const uint8_t *__res
         const uint64_t p = base + 16ull * (uint32_t)lane;
         uint32_t m = 0;
         if (p < b) {
-            const uint4 v = load16(text, n_bytes, p, 0u);
+            const uint4 v = load16(text, n_bytes, p);
             uint32_t prev = p > a ? text[p - 1] : 0u;  // (the byte before the record never joins a "\r\n")
 #pragma unroll
             for (int j = 0; j < 16; j++) {
@@ -365,7 +322,7 @@ __global__ __launch_bounds__(CT_) void apply_records_kernel(const uint8_t *__res
         uint32_t nb = 0;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (p < e2) {
-            v = load16(text, n_bytes, p, 0u);
+            v = load16(text, n_bytes, p);
 #pragma unroll
             for (int j = 0; j < 16; j++)
                 if (p + j >= s2 && p + j < e2 && byte_of(v, j) != ' ') nb |= 1u << j;

@@ -26,7 +26,7 @@
 //           common.h (the format kernels' scan); its last status word is the
 //           text size.
 //   copy    (pass 2) one block per KMAN_CUT_TILE output bytes.  Thread 0 cuts
-//           the slice of E that covers the tile (two upper bounds); a slice of
+//           the slice of E that covers the tile (tile_records.h); a slice of
 //           <= KMAN_CUT_SEG_CAP segments is staged in LDS, a larger one (many
 //           records of a few bytes, or long rows of unlisted ones) is searched
 //           in global memory.  A thread owns 16-byte output words, 4096 B
@@ -39,12 +39,13 @@
 //           in the text's last word.  Work per block does not depend on the
 //           records' lengths.
 //
-// Bounds, not values: record offsets are clamped to n_bytes and a descending
-// pair is an empty record; every line search ends at the record's end; a text
+// Bounds, not values: tile_records.h for the slice of E; record offsets are
+// clamped to n_bytes and a descending pair is an empty record; every line search ends at the record's end; a text
 // byte is read only below n_bytes, an output byte written only below the text
 // size, which the host has checked against cap before pass 2 is launched.
-// Every search runs a step count fixed before it starts.
+#include "bytes16.h"
 #include "common.h"
+#include "tile_records.h"
 
 namespace {
 
@@ -55,38 +56,6 @@ constexpr int SCAN_E = 8;
 constexpr int SCAN_TILE = CT * SCAN_E;
 constexpr uint64_t NOPOS = ~0ull;
 static_assert(TILE % (16 * CT) == 0, "a tile is whole rounds of one 16-byte word per thread");
-
-KMAN_DEV uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
-// the number of entries of e[0, n) that are <= b (screen.hip's)
-KMAN_DEV uint64_t upper_count(const uint64_t *e, uint64_t n, uint64_t b) {
-    uint64_t lo = 0, len = n;
-    for (int s = 0; s < 64 && len; s++) {
-        const uint64_t half = len >> 1;
-        if (e[lo + half] <= b) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
-}
-
-// the 16-byte word of the text at p (p % 16 == 0); bytes at or past n_bytes read as 0
-KMAN_DEV uint4 load16(const uint8_t *__restrict__ text, uint64_t n_bytes, uint64_t p) {
-    if (p + 16 <= n_bytes) return *reinterpret_cast<const uint4 *>(text + p);
-    uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 16; j++)
-        if (p + j < n_bytes) w[j >> 2] |= (uint32_t)text[p + j] << (8 * (j & 3));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-KMAN_DEV uint32_t byte_of(const uint4 &v, int j) {
-    const uint32_t w = (j >> 2) == 0 ? v.x : (j >> 2) == 1 ? v.y : (j >> 2) == 2 ? v.z : v.w;
-    return (w >> (8 * (j & 3))) & 0xffu;
-}
 
 // what the parser's right strip removes from a sequence line
 KMAN_DEV bool is_strip(uint32_t c) { return c == ' ' || c == '\t' || c == 0x0b || c == 0x0c || (c >= 0x1c && c <= 0x1f); }
@@ -114,14 +83,6 @@ __global__ __launch_bounds__(CT) void cut_whole_kernel(const uint64_t *__restric
     const bool kept = !keep || keep[r] != 0;
     E[r] = kept && b > a ? b - a : 0;
     src[r] = a;
-}
-
-// the first byte of the line after the terminator that starts at t (t >= b: none)
-KMAN_DEV uint64_t line_after(const uint8_t *__restrict__ text, uint64_t t, uint64_t b) {
-    if (t >= b) return b;
-    uint64_t n = t + 1;
-    if (text[t] == '\r' && n < b && text[n] == '\n') n++;
-    return n;
 }
 
 // pass 1, trimmed FASTQ records: one wave per record
@@ -261,46 +222,26 @@ __global__ __launch_bounds__(CT) void cut_copy_kernel(const uint8_t *__restrict_
     const uint64_t lo = (uint64_t)blockIdx.x * TILE;
     const uint64_t hi = umin64(lo + TILE, total);  // (lo < total: the grid is ceil(total / TILE))
     if (threadIdx.x == 0) {
-        // the segments that hold output bytes [lo, hi): from the last one that
-        // starts at or before lo to the last one that starts at or before hi - 1
-        const uint64_t u0 = upper_count(E, nseg, lo), u1 = upper_count(E, nseg, hi - 1);
-        const uint64_t i0 = u0 ? u0 - 1 : 0;
-        s_i0 = i0;
-        s_ns = u1 > i0 ? u1 - i0 : 0;
+        const TileSlice s = cut_slice(E, nseg, lo, hi - 1);  // the segments that hold output bytes [lo, hi)
+        s_i0 = s.r0;
+        s_ns = s.ns;
     }
     __syncthreads();
     const uint64_t i0 = s_i0, ns = s_ns;
     if (ns == 0) return;  // (cannot happen: E[0] = 0 <= lo)
-    const bool big = ns > (uint64_t)SEG_CAP;
-    if (!big) {
-        for (uint32_t i = threadIdx.x; i <= (uint32_t)ns; i += CT) sE[i] = E[i0 + i];  // (i0 + ns <= nseg)
-        for (uint32_t i = threadIdx.x; i < (uint32_t)ns; i += CT) sS[i] = src[i0 + i];
-        __syncthreads();
-    }
-    const uint64_t *es = big ? E + i0 : sE;
-    const uint64_t *ss = big ? src + i0 : sS;
+    // (E has nseg + 1 entries and i0 + ns <= nseg: the tail is E's own entry)
+    const uint64_t *es = stage_slice<CT, SEG_CAP, TAIL_ENTRY>(E, {i0, ns, 0}, sE).rs;
+    const uint64_t *ss = stage_slice<CT, SEG_CAP>(src, {i0, ns, 0}, sS).rs;
+    if (ns <= (uint64_t)SEG_CAP) __syncthreads();  // (block-uniform)
 
     for (uint64_t o = lo + 16ull * threadIdx.x; o < hi; o += 16ull * CT) {
         const uint64_t u = upper_count(es, ns, o);
         uint64_t i = u ? u - 1 : 0;
         uint64_t seg = es[i], end = es[i + 1];
         const uint64_t s = ss[i] + (o - seg);
-        uint4 w;
         if (o + 16 <= hi && o >= seg && o + 16 + nl <= end && s + 16 <= n_bytes) {
-            // sixteen text bytes of one segment: the words at s - s % 16 and after it, shifted
-            const uint32_t q = (uint32_t)(s & 15), dq = q >> 2, sh = q & 3;
-            const uint4 A = load16(text, n_bytes, s - q);
-            const uint4 B = q ? load16(text, n_bytes, s - q + 16) : make_uint4(0, 0, 0, 0);
-            const uint32_t x0 = dq == 0 ? A.x : dq == 1 ? A.y : dq == 2 ? A.z : A.w;
-            const uint32_t x1 = dq == 0 ? A.y : dq == 1 ? A.z : dq == 2 ? A.w : B.x;
-            const uint32_t x2 = dq == 0 ? A.z : dq == 1 ? A.w : dq == 2 ? B.x : B.y;
-            const uint32_t x3 = dq == 0 ? A.w : dq == 1 ? B.x : dq == 2 ? B.y : B.z;
-            const uint32_t x4 = dq == 0 ? B.x : dq == 1 ? B.y : dq == 2 ? B.z : B.w;
-            w.x = __builtin_amdgcn_alignbyte(x1, x0, sh);
-            w.y = __builtin_amdgcn_alignbyte(x2, x1, sh);
-            w.z = __builtin_amdgcn_alignbyte(x3, x2, sh);
-            w.w = __builtin_amdgcn_alignbyte(x4, x3, sh);
-            *reinterpret_cast<uint4 *>(out + o) = w;
+            // sixteen text bytes of one segment
+            *reinterpret_cast<uint4 *>(out + o) = shifted16(text, n_bytes, s);
             continue;
         }
         uint32_t x[4] = {0, 0, 0, 0};

@@ -6,7 +6,7 @@
 // lines to a multiple of four; line 4r is record r's '@' header, 4r + 1 its
 // sequence, 4r + 2 the '+' separator and 4r + 3 the quality, which must be as
 // long as line 4r + 1.  The sequence line is cleaned as a FASTA sequence line
-// (right-stripped, ' ' and '\r' removed, parse.hip's codes4 per byte).
+// (right-stripped, ' ' and '\r' removed, swar.h's codes4 per byte).
 //
 // The only non-local fact of a byte is its line kind = (line starts up to and
 // including it - 1) mod 4.  A chunk's summary is its line count and, for each
@@ -32,6 +32,7 @@
 // on) is below the threshold has its code turned into that of an 'N'.  See the
 // kernel for its traffic.
 #include "common.h"
+#include "swar.h"
 
 namespace {
 
@@ -81,13 +82,7 @@ KMAN_DEV Q lq_id() {
     return q;
 }
 
-KMAN_DEV bool is_term(uint32_t c) { return c == '\n' || c == '\r'; }
-// Python str.isspace() over ASCII: what str.rstrip() strips.
-KMAN_DEV bool py_space(uint32_t c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x1f); }
-
-// SWAR byte tests on 4 packed bytes: 0x80 in every byte that passes
-KMAN_DEV uint32_t zero_bytes(uint32_t t) { return ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t | 0x7f7f7f7fu); }
-KMAN_DEV uint32_t eq_bytes(uint32_t w, uint32_t c) { return zero_bytes(w ^ (c * 0x01010101u)); }
+// (SWAR byte tests on 4 packed bytes, as swar.h's: 0x80 in every byte that passes)
 // bytes below c (c <= 0x80)
 KMAN_DEV uint32_t lt_bytes(uint32_t w, uint32_t c) {
     return ~((w & 0x7f7f7f7fu) + (0x80u - c) * 0x01010101u) & ~w & 0x80808080u;
@@ -98,22 +93,6 @@ KMAN_DEV uint32_t lt_bytes_u8(uint32_t w, uint32_t c) {
     const uint32_t lo7 = ~((w & 0x7f7f7f7fu) + (0x80u - (hi ? c - 0x80u : c)) * 0x01010101u) & 0x80808080u;
     return hi ? ((~w & 0x80808080u) | (lo7 & w)) : (lo7 & ~w);
 }
-// the 0x80 bits of four bytes -> a 4-bit mask
-KMAN_DEV uint32_t hibits4(uint32_t m) {
-    m >>= 7;
-    return (m | (m >> 7) | (m >> 14) | (m >> 21)) & 0xfu;
-}
-// base codes of four bytes (A/a 0, C/c 1, G/g 2, T/t 3, else 4): parse.hip's rule
-KMAN_DEV uint32_t codes4(uint32_t w) {
-    const uint32_t x = (w >> 1) & 0x03030303u;
-    const uint32_t code = x ^ ((x >> 1) & 0x01010101u);
-    const uint32_t y = w | 0x20202020u;
-    const uint32_t ok = eq_bytes(y, 'a') | eq_bytes(y, 'c') | eq_bytes(y, 'g') | eq_bytes(y, 't');
-    return (code & ((ok >> 7) * 3u)) | ((~ok & 0x80808080u) >> 5);
-}
-KMAN_DEV uint32_t byte_at(const uint32_t (&w)[PB / 4], int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
-KMAN_DEV uint64_t bits_from(int i) { return i >= 64 ? 0ull : (~0ull << i); }
-KMAN_DEV uint64_t bits_below(int i) { return i >= 64 ? ~0ull : ((1ull << i) - 1); }
 // bit i = xor of bits 0..i
 KMAN_DEV uint64_t prefix_xor(uint64_t x) {
     x ^= x << 1;

@@ -39,6 +39,7 @@
 // read only below n_bases; an output byte is written only below the tile's
 // offset plus its kept count, at most n_bases; both record loops run a step
 // count fixed before they start.
+#include "bytes16.h"
 #include "common.h"
 
 namespace {
@@ -50,21 +51,6 @@ constexpr int HTILE = (HT / 64) * HWAVE;  // bytes per tile
 constexpr int GROUP = KMAN_HPC_GROUP;
 static_assert(HTILE == KMAN_HPC_TILE, "include/kman.h states the tile size");
 static_assert(GROUP == 16 * 16, "sixteen lanes' words make a prefix group");
-
-// the aligned 16-byte word of src at p (p % 16 == 0); bytes at or past n read as 0
-KMAN_DEV uint4 load16(const uint8_t *__restrict__ src, uint64_t n, uint64_t p) {
-    if (p < n && n - p >= 16) return *reinterpret_cast<const uint4 *>(src + p);
-    auto dword = [&](int d) -> uint32_t {
-        uint32_t acc = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const uint64_t q = p + (uint64_t)(4 * d + b);
-            if (q < n) acc |= (uint32_t)src[q] << (8 * b);
-        }
-        return acc;
-    };
-    return make_uint4(dword(0), dword(1), dword(2), dword(3));
-}
 
 // the four bytes of w that are KEPT, as bits 0-3; prev: the byte before w's first
 KMAN_DEV uint32_t keep4(uint32_t w, uint32_t prev) {

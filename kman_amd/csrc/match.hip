@@ -57,12 +57,10 @@ constexpr int MPAD = 8;                  // LDS rows for the alignment offsets a
 static_assert(MTILE == KMAN_MATCH_TILE, "include/kman.h states the tile size");
 static_assert((MTILE + 1) >> MSTEPS == 0, "MSTEPS halvings empty the B slice");
 
-KMAN_DEV uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
 // the number of A rows among the first d rows of the merged order, ties A first
 KMAN_DEV uint64_t merge_split(const uint64_t *__restrict__ ak, uint64_t na, const uint64_t *__restrict__ bk,
                               uint64_t nb, uint64_t d) {
-    uint64_t lo = d > nb ? d - nb : 0, hi = min64(d, na);
+    uint64_t lo = d > nb ? d - nb : 0, hi = umin64(d, na);
     for (int s = 0; s < 64 && lo < hi; s++) {
         const uint64_t mid = lo + ((hi - lo) >> 1);  // (lo <= mid < hi <= d, mid >= d - nb: 0 <= d - 1 - mid < nb)
         if (ak[mid] <= bk[d - 1 - mid]) lo = mid + 1;
@@ -76,7 +74,7 @@ __global__ __launch_bounds__(MT) void match_split(const uint64_t *__restrict__ a
                                                   uint64_t *__restrict__ split) {
     const uint64_t t = (uint64_t)blockIdx.x * MT + threadIdx.x;
     if (t > tiles) return;
-    split[t] = merge_split(ak, na, bk, nb, min64(t * MTILE, na + nb));
+    split[t] = merge_split(ak, na, bk, nb, umin64(t * MTILE, na + nb));
 }
 
 // Rows [i0, i1) of src (n rows in all) to LDS: dst[i - base] = src[i], where
@@ -131,15 +129,15 @@ __global__ __launch_bounds__(MT) void match_tile(const uint64_t *__restrict__ ak
     const bool need_a = op != KMAN_MATCH_RIGHT;
     const bool need_b = op != KMAN_MATCH_LEFT && op != KMAN_MATCH_ABSENT;
     const uint64_t N = na + nb;
-    const uint64_t d0 = min64((uint64_t)blockIdx.x * MTILE, N), d1 = min64(d0 + MTILE, N);
+    const uint64_t d0 = umin64((uint64_t)blockIdx.x * MTILE, N), d1 = umin64(d0 + MTILE, N);
     // the clamps change nothing for sorted input (a_t <= a_t+1 <= a_t + d1 - d0)
-    const uint64_t a0 = min64(split[blockIdx.x], min64(d0, na));
+    const uint64_t a0 = umin64(split[blockIdx.x], umin64(d0, na));
     uint64_t a1 = split[blockIdx.x + 1];
-    a1 = a1 < a0 ? a0 : min64(a1, min64(a0 + (d1 - d0), na));
+    a1 = a1 < a0 ? a0 : umin64(a1, umin64(a0 + (d1 - d0), na));
     const uint32_t nA = (uint32_t)(a1 - a0);
     if (nA == 0) return;  // a tile of B rows only: nothing to write
-    const uint64_t b0 = min64(d0 - a0, nb), b1 = min64(d1 - a1, nb);
-    const uint64_t b1x = min64((b1 < b0 ? b0 : b1) + 1, nb);  // B's slice and the row past it
+    const uint64_t b0 = umin64(d0 - a0, nb), b1 = umin64(d1 - a1, nb);
+    const uint64_t b1x = umin64((b1 < b0 ? b0 : b1) + 1, nb);  // B's slice and the row past it
     const uint32_t nB = (uint32_t)(b1x - b0);                 // <= MTILE - nA + 1
     // this thread's A counts: in flight while the slices are staged
     uint64_t ca[MROWS];

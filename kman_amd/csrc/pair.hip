@@ -15,8 +15,8 @@
 //            last segment is n_bases1 + n_bases2.
 //   copy     one block per KMAN_ZIP_TILE output bytes.  The block cuts the
 //            slice of d_rec_seq that covers the tile with two block-wide upper
-//            bounds (256 probes per step, at most 8 steps); a slice of <=
-//            KMAN_ZIP_SEG_CAP segments is staged in LDS with the segments'
+//            bounds (tile_records.h: 256 probes per step, at most 8 steps); a
+//            slice of <= KMAN_ZIP_SEG_CAP segments is staged in LDS with the segments'
 //            source offsets, a larger one (1-base and empty mates) is searched
 //            in global memory.  A thread owns aligned 16-byte output words,
 //            4096 B apart: an upper bound finds the word's segment, and the
@@ -29,12 +29,14 @@
 //            the total are written as 4, the pad's value.
 //   pad      the bytes from the last word's end to total + 64: a memset of 4.
 //
-// Bounds, not values: table entries are clamped to n_bases; a source byte is
-// read only below its n_bases (a byte that a wrong table asks for past it
+// Bounds, not values: tile_records.h for the slice; table entries are clamped
+// to n_bases; a source byte is read only below its n_bases (a byte that a wrong table asks for past it
 // reads as 0); an output word is written only below total rounded up to 16,
 // which the caller's total + 64 bytes hold.  Every search and every piece loop
 // runs a step count fixed before it starts.
+#include "bytes16.h"
 #include "common.h"
+#include "tile_records.h"
 
 namespace {
 
@@ -43,82 +45,6 @@ constexpr uint32_t TILE = KMAN_ZIP_TILE;
 constexpr int SEG_CAP = KMAN_ZIP_SEG_CAP;
 constexpr uint32_t PAD4 = 0x04040404u;
 static_assert(TILE % (16 * ZT) == 0, "a tile is whole rounds of one 16-byte word per thread");
-
-KMAN_DEV uint64_t zmin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
-// the number of entries of e[0, n) that are <= b (screen.hip's)
-KMAN_DEV uint64_t upper_count(const uint64_t *e, uint64_t n, uint64_t b) {
-    uint64_t lo = 0, len = n;
-    for (int s = 0; s < 64 && len; s++) {
-        const uint64_t half = len >> 1;
-        if (e[lo + half] <= b) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
-}
-
-// the same by the whole block: every step probes the last entry of ZT equal
-// chunks of the range and keeps the first chunk whose last entry is > b (8
-// steps cover 2^64 entries).  Every thread returns the same number.
-KMAN_DEV uint64_t block_upper_count(const uint64_t *__restrict__ e, uint64_t n, uint64_t b, uint32_t *lds_cnt) {
-    uint64_t lo = 0, len = n;
-    for (int s = 0; s < 8 && len; s++) {
-        const uint64_t chunk = (len + ZT - 1) / ZT;
-        const uint64_t first = (uint64_t)threadIdx.x * chunk;
-        bool le = false;
-        if (first < len) le = e[lo + zmin64(first + chunk, len) - 1] <= b;
-        const uint64_t bal = __ballot(le);
-        if (lane_id() == 0) lds_cnt[threadIdx.x >> 6] = (uint32_t)__popcll((unsigned long long)bal);
-        __syncthreads();
-        uint32_t c = 0;
-#pragma unroll
-        for (int w = 0; w < ZT / 64; w++) c += lds_cnt[w];
-        __syncthreads();
-        // chunks [0, c) are <= b throughout (ascending entries); the answer lies in chunk c, before its last entry
-        const uint64_t skip = zmin64((uint64_t)c * chunk, len);
-        lo += skip;
-        len -= skip;
-        len = len ? zmin64(chunk, len) - 1 : 0;
-    }
-    return lo;
-}
-
-// the aligned 16-byte word of src at p (p % 16 == 0); bytes at or past n read as 0
-KMAN_DEV uint4 load16(const uint8_t *__restrict__ src, uint64_t n, uint64_t p) {
-    if (p < n && n - p >= 16) return *reinterpret_cast<const uint4 *>(src + p);
-    auto dword = [&](int d) -> uint32_t {
-        uint32_t acc = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const uint64_t q = p + (uint64_t)(4 * d + b);
-            if (q < n) acc |= (uint32_t)src[q] << (8 * b);
-        }
-        return acc;
-    };
-    return make_uint4(dword(0), dword(1), dword(2), dword(3));
-}
-
-// the sixteen bytes of src from a on (any alignment): the words at a - a % 16 and after it, shifted
-KMAN_DEV uint4 shifted16(const uint8_t *__restrict__ src, uint64_t n, uint64_t a) {
-    const uint32_t q = (uint32_t)(a & 15), dq = q >> 2, sh = q & 3;
-    const uint4 A = load16(src, n, a - q);
-    const uint4 B = q ? load16(src, n, a - q + 16) : make_uint4(0, 0, 0, 0);
-    const uint32_t x0 = dq == 0 ? A.x : dq == 1 ? A.y : dq == 2 ? A.z : A.w;
-    const uint32_t x1 = dq == 0 ? A.y : dq == 1 ? A.z : dq == 2 ? A.w : B.x;
-    const uint32_t x2 = dq == 0 ? A.z : dq == 1 ? A.w : dq == 2 ? B.x : B.y;
-    const uint32_t x3 = dq == 0 ? A.w : dq == 1 ? B.x : dq == 2 ? B.y : B.z;
-    const uint32_t x4 = dq == 0 ? B.x : dq == 1 ? B.y : dq == 2 ? B.z : B.w;
-    uint4 w;
-    w.x = __builtin_amdgcn_alignbyte(x1, x0, sh);
-    w.y = __builtin_amdgcn_alignbyte(x2, x1, sh);
-    w.z = __builtin_amdgcn_alignbyte(x3, x2, sh);
-    w.w = __builtin_amdgcn_alignbyte(x4, x3, sh);
-    return w;
-}
 
 // the bytes [j0, j1) of a 16-byte word (0 <= j0 < j1 <= 16) that lie in its dword d, as a mask
 KMAN_DEV uint32_t dword_mask(int j0, int j1, int d) {
@@ -134,7 +60,7 @@ __global__ __launch_bounds__(ZT) void zip_offsets_kernel(const uint64_t *__restr
                                                          uint64_t n2, uint64_t *__restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * ZT + threadIdx.x;
     if (i >= R) return;
-    const uint64_t a = zmin64(rs1[i], n1), b = i + 1 < R ? zmin64(rs1[i + 1], n1) : n1, c = zmin64(rs2[i], n2);
+    const uint64_t a = umin64(rs1[i], n1), b = i + 1 < R ? umin64(rs1[i + 1], n1) : n1, c = umin64(rs2[i], n2);
     out[2 * i] = a + c;
     out[2 * i + 1] = b + c;
 }
@@ -146,7 +72,7 @@ KMAN_DEV uint64_t seg_off(const uint64_t *__restrict__ O, uint64_t nseg, uint64_
 }
 KMAN_DEV uint64_t seg_src(const uint64_t *__restrict__ rs1, uint64_t n1, const uint64_t *__restrict__ rs2, uint64_t n2,
                           uint64_t j) {
-    return (j & 1) ? zmin64(rs2[j >> 1], n2) : zmin64(rs1[j >> 1], n1);
+    return (j & 1) ? umin64(rs2[j >> 1], n2) : umin64(rs1[j >> 1], n1);
 }
 
 // the tile's words.  Entry k of the slice is segment i0 + k: its offsets (ns + 1)
@@ -161,20 +87,20 @@ KMAN_DEV void zip_words(const uint8_t *__restrict__ codes1, uint64_t n1, const u
     auto source = [&](uint64_t k) -> uint64_t { return BIG ? seg_src(rs1, n1, rs2, n2, i0 + k) : sS[k]; };  // k < ns
     const uint64_t *es = BIG ? O + i0 : sE;  // (upper_count reads entries [0, ns) only, and i0 + ns <= nseg)
     for (uint64_t o = lo + 16ull * threadIdx.x; o < hi; o += 16ull * ZT) {
-        const uint64_t wend = zmin64(o + 16, hi);
+        const uint64_t wend = umin64(o + 16, hi);
         uint32_t x0 = PAD4, x1 = PAD4, x2 = PAD4, x3 = PAD4;  // (what no segment covers stays 4)
         uint64_t pos = o, cand = 0;  // cand - 1: the segment that starts at pos (0: not known)
         for (int it = 0; it < 17 && pos < wend; it++) {
             // the segment that holds pos: the one that starts there, or, when that one is empty, a search
             const uint64_t u = cand && cand <= ns && off(cand) > pos ? cand : upper_count(es, ns, pos);
             if (u == 0) {  // before the first segment (ns == 0: before the first entry, or the total)
-                pos = zmin64(off(0), wend);
+                pos = umin64(off(0), wend);
                 cand = 1;
                 continue;
             }
             const uint64_t i = u - 1;
             cand = u + 1;
-            const uint64_t seg = off(i), pe = zmin64(off(i + 1), wend);
+            const uint64_t seg = off(i), pe = umin64(off(i + 1), wend);
             if (pe <= pos) break;  // (a table that is not ascending)
             const bool second = ((i0 + i) & 1) != 0;
             const uint8_t *__restrict__ src = second ? codes2 : codes1;
@@ -219,12 +145,12 @@ __global__ __launch_bounds__(ZT) void zip_copy_kernel(const uint8_t *__restrict_
     __shared__ uint64_t sS[SEG_CAP];
     __shared__ uint32_t s_cnt[ZT / 64];
     const uint64_t lo = (uint64_t)blockIdx.x * TILE;
-    const uint64_t hi = zmin64(lo + TILE, total);  // (lo < total: the grid is ceil(total / TILE))
+    const uint64_t hi = umin64(lo + TILE, total);  // (lo < total: the grid is ceil(total / TILE))
     // the segments that hold output bytes [lo, hi): from the last one that
     // starts at or before lo to the last one that starts at or before hi - 1
-    const uint64_t u0 = block_upper_count(O, nseg, lo, s_cnt), u1 = block_upper_count(O, nseg, hi - 1, s_cnt);
-    const uint64_t i0 = u0 ? u0 - 1 : 0;
-    const uint64_t ns = u1 > i0 ? u1 - i0 : 0;  // (0: the tile lies before the first segment)
+    const uint64_t u0 = block_upper_count<ZT>(O, nseg, lo, s_cnt), u1 = block_upper_count<ZT>(O, nseg, hi - 1, s_cnt);
+    const TileSlice sl = slice_of(u0, u1);
+    const uint64_t i0 = sl.r0, ns = sl.ns;  // (ns == 0: the tile lies before the first segment)
     if (ns > (uint64_t)SEG_CAP) {
         zip_words<true>(codes1, n1, codes2, n2, rs1, rs2, O, nseg, total, nullptr, nullptr, i0, ns, lo, hi, out);
         return;

@@ -41,6 +41,7 @@
 #include "common.h"
 #include "kmer.h"
 #include "screen_lookup.h"
+#include "tile_records.h"
 
 namespace {
 
@@ -107,21 +108,6 @@ void launch_window_counts(kman_ctx *ctx, const uint8_t *codes, uint64_t n_bases,
 }
 
 // ------------------------------------------------------------ record quantile
-
-// the number of entries of rs[0, n) that are < x
-KMAN_DEV uint64_t lower_count(const uint64_t *rs, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, len = n;
-    for (int s = 0; s < 64 && len; s++) {
-        const uint64_t half = len >> 1;
-        if (rs[lo + half] < x) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
-}
 
 // LDS writes of this wave before, its LDS reads after
 KMAN_DEV void wave_sync_lds() {
@@ -202,15 +188,15 @@ __global__ __launch_bounds__(QT) void record_quantile_kernel(const uint32_t *__r
         uint64_t rhi = cb + QC > n_bases ? n_records : lower_count(rec_seq, n_records, cb + QC);
         if (rhi < rlo) rhi = rlo;  // (unsorted entries)
         // staged: the chunk, and the tail of its last record when that one is short
-        uint64_t need = smin64(cb + QC, n_bases);
+        uint64_t need = umin64(cb + QC, n_bases);
         if (rhi > rlo) {
-            const uint64_t s = smin64(rec_seq[rhi - 1], n_bases);
-            const uint64_t e = rhi < n_records ? smin64(rec_seq[rhi], n_bases) : n_bases;
+            const uint64_t s = umin64(rec_seq[rhi - 1], n_bases);
+            const uint64_t e = rhi < n_records ? umin64(rec_seq[rhi], n_bases) : n_bases;
             if (e > need && e >= s && e - s <= (uint64_t)QCAP) need = e;
         }
         s_rlo = rlo;
         s_rhi = rhi;
-        s_need = smin64(need, cb + QR);
+        s_need = umin64(need, cb + QR);
     }
     __syncthreads();
     const uint64_t rlo = s_rlo, rhi = s_rhi, need = s_need;
@@ -219,7 +205,7 @@ __global__ __launch_bounds__(QT) void record_quantile_kernel(const uint32_t *__r
     const bool staged = ns <= (uint64_t)QSLICE;
     if (staged)
         for (uint32_t i = threadIdx.x; i <= (uint32_t)ns; i += QT)
-            srec[i] = rlo + i < n_records ? smin64(rec_seq[rlo + i], n_bases) : n_bases;
+            srec[i] = rlo + i < n_records ? umin64(rec_seq[rlo + i], n_bases) : n_bases;
     for (uint32_t i = threadIdx.x; i < (uint32_t)(QR / 4); i += QT) {
         const uint64_t b = cb + 4ull * i;
         if (b + 4 <= need) {
@@ -239,8 +225,8 @@ __global__ __launch_bounds__(QT) void record_quantile_kernel(const uint32_t *__r
             s = srec[r - rlo];
             e = srec[r - rlo + 1];
         } else {
-            s = smin64(rec_seq[r], n_bases);
-            e = r + 1 < n_records ? smin64(rec_seq[r + 1], n_bases) : n_bases;
+            s = umin64(rec_seq[r], n_bases);
+            e = r + 1 < n_records ? umin64(rec_seq[r + 1], n_bases) : n_bases;
         }
         if (s < cb || s - cb >= (uint64_t)QC) continue;  // (unsorted entries: not this chunk's)
         const uint64_t len = e > s ? e - s : 0;

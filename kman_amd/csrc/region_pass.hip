@@ -269,9 +269,6 @@ __global__ __launch_bounds__(NT_, 4) void rg_pass(PassArgs pa, uint32_t *__restr
                 // (line1, a test setting: one line per digit at any width)
                 const uint32_t lb = pa.line1 ? 0u : 9u - bits, lm = (1u << lb) - 1, RING = 32u << lb;
                 if (threadIdx.x < RB) {
-                    struct MaxU32 {
-                        KMAN_DEV uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
-                    };
                     const uint32_t rn = run[threadIdx.x];
                     const uint32_t nl = ((rn + thist[threadIdx.x]) >> 5) - (rn >> 5);
                     const uint32_t m = wave_inclusive_scan(nl, MaxU32(), 0u);

@@ -24,10 +24,6 @@ constexpr int RT = 256;
 constexpr int RI = 16;
 constexpr int RTILE = RT * RI;
 
-struct MaxU64 {
-    KMAN_DEV uint64_t operator()(uint64_t a, uint64_t b) const { return a > b ? a : b; }
-};
-
 KMAN_DEV void stage_keys(const uint64_t *__restrict__ keys, uint64_t n, uint64_t tb, uint64_t *s) {
     for (int i = threadIdx.x; i < RTILE; i += RT) {
         const uint64_t idx = tb + i;

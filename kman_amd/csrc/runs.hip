@@ -19,11 +19,10 @@
 //   scan        one block of 1024 threads: the exclusive max-scan of those
 //               words over the tiles, in place, 8192 tiles per round.
 //   runs        (pass 2) one block per tile.  Thread 0 cuts the slice of
-//               d_rec_seq that owns the tile's bases (screen_kernel's two upper
-//               bounds); a slice of <= RCAP entries is staged in LDS, a larger
-//               one (many empty or one-base records) is searched in global
-//               memory.  A thread turns its 16 words (four 16-byte loads) into
-//               a bit mask, the block max-scans the threads' last breaks (DPP
+//               d_rec_seq that owns the tile's bases; a slice of <= RCAP
+//               entries is staged in LDS, a larger one is searched in global
+//               memory (tile_records.h).  A thread turns its 16 words (four
+//               16-byte loads) into a bit mask, the block max-scans the threads' last breaks (DPP
 //               wave scans, one barrier), then the thread walks its 16 bases
 //               and searches the slice again only where a base passes the next
 //               record's first base.  At a run's end (the next base is not
@@ -46,18 +45,16 @@
 // Integer max / min commute, every other store is the only one to its word:
 // the same bytes on every call.
 //
-// Bounds, not values: every record index comes from a search over at most
-// n_records entries with a step count fixed before it starts and is checked
-// against n_records before it addresses the output; a record's first base is
-// taken as min(entry, the base it owns), so every slot is < RTILE and every
-// run start is <= its end; the slice index never passes ns (entry ns: the
-// first base of the next record, or n_bases).  An unsorted d_rec_seq gives
-// wrong (or unwritten) words, never a wild address or an unbounded loop.
+// Bounds, not values: tile_records.h for the slice; here every record index is
+// checked against n_records before it addresses the output, and a record's
+// first base is taken as min(entry, the base it owns), so every slot is <
+// RTILE and every run start is <= its end.
 //
 // Algorithmic bytes: the words are read at most twice (pass 1 stops early), 8 B
 // per base; 56 B of work memory per tile written and read; 16 B written per
 // record.
 #include "common.h"
+#include "tile_records.h"
 
 namespace {
 
@@ -76,31 +73,7 @@ static_assert(BEFORE < (1u << 13), "the low key field has 13 bits");
 
 #define WC_NONE KMAN_WC_NONE
 
-struct MaxU32 {
-    KMAN_DEV uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
-};
-struct MaxU64 {
-    KMAN_DEV uint64_t operator()(uint64_t a, uint64_t b) const { return a > b ? a : b; }
-};
-
-KMAN_DEV uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-KMAN_DEV uint64_t umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
 KMAN_DEV bool is_solid(uint32_t w, uint32_t min_count) { return w != WC_NONE && w >= min_count; }
-
-// the number of entries of rs[0, n) that are <= b (screen.hip's)
-KMAN_DEV uint64_t upper_count(const uint64_t *rs, uint64_t n, uint64_t b) {
-    uint64_t lo = 0, len = n;
-    for (int s = 0; s < 64 && len; s++) {
-        const uint64_t half = len >> 1;
-        if (rs[lo + half] <= b) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
-}
 
 // pass 1: agg[t] = 1 + the position of tile t's last non-solid base, 0 when it has none
 __global__ __launch_bounds__(RT) void runs_last_break_kernel(const uint32_t *__restrict__ wc, uint64_t n_bases,
@@ -170,14 +143,10 @@ __global__ __launch_bounds__(RT) void runs_kernel(const uint32_t *__restrict__ w
     const uint64_t tb = (uint64_t)blockIdx.x * RTILE;
     const uint64_t tend = umin64(tb + RTILE, n_bases);  // (tb < n_bases: the grid is ceil(n_bases / RTILE))
     if (threadIdx.x == 0) {
-        // the records that own bases [tb, tend): from the owner of tb (or the
-        // first record, when none starts at or before tb) to the owner of tend - 1
-        const uint64_t u0 = upper_count(rec_seq, n_records, tb), u1 = upper_count(rec_seq, n_records, tend - 1);
-        const uint64_t r0 = u0 ? u0 - 1 : 0;
-        const uint64_t ns = u1 > r0 ? u1 - r0 : 0;
-        s_r0 = r0;
-        s_ns = ns;
-        s_next = r0 + ns < n_records ? umin64(rec_seq[r0 + ns], n_bases) : n_bases;
+        const TileSlice s = cut_slice(rec_seq, n_records, tb, tend - 1, n_bases);  // the records that own [tb, tend)
+        s_r0 = s.r0;
+        s_ns = s.ns;
+        s_next = s.next;
     }
     // the thread's 16 words as a mask of solid bases (past n_bases: not solid)
     const uint64_t p0 = tb + (uint64_t)threadIdx.x * REI;
@@ -204,9 +173,7 @@ __global__ __launch_bounds__(RT) void runs_kernel(const uint32_t *__restrict__ w
     __syncthreads();
     const uint64_t r0 = s_r0, ns = s_ns, next = s_next;
     if (ns == 0) return;  // (no record starts at or before the tile's last base)
-    const bool big = ns > (uint64_t)RCAP;
-    if (!big)
-        for (uint32_t i = threadIdx.x; i <= (uint32_t)ns; i += RT) srec[i] = i < (uint32_t)ns ? rec_seq[r0 + i] : next;
+    const SliceView sv = stage_slice<RT, RCAP, TAIL_NEXT>(rec_seq, {r0, ns, next}, srec);
     for (uint32_t i = threadIdx.x; i < (uint32_t)(RTILE / 2); i += RT)
         reinterpret_cast<uint4 *>(skey)[i] = make_uint4(0, 0, 0, 0);
     s_first[threadIdx.x] = (uint8_t)(m & 1u);
@@ -216,9 +183,7 @@ __global__ __launch_bounds__(RT) void runs_kernel(const uint32_t *__restrict__ w
     const uint32_t ex = block_exclusive_scan1<RT>(mine, MaxU32(), 0u, s_scan, (uint32_t *)nullptr);
     // (the barrier inside the scan: srec, skey and s_first are written)
 
-    const uint64_t *rs = big ? rec_seq + r0 : srec;
-    // entry i <= ns of the slice; entry ns: the first base of the next record, or n_bases
-    auto ent = [&](uint64_t i) -> uint64_t { return i < ns ? rs[i] : next; };
+    const uint64_t *rs = sv.rs;
 
     if (m) {
         const bool right_solid = threadIdx.x == RT - 1 ? after_solid : (s_first[threadIdx.x + 1] != 0);
@@ -226,7 +191,7 @@ __global__ __launch_bounds__(RT) void runs_kernel(const uint32_t *__restrict__ w
         uint64_t u = upper_count(rs, ns, p0);
         bool owned = u != 0;                                   // (false: bases before the first record)
         uint64_t cur = owned ? umin64(rs[u - 1], p0) : p0;     // the first base of the current record
-        uint64_t nxt = ent(u);                                 // the base where the owner changes
+        uint64_t nxt = sv.ent(u);                                 // the base where the owner changes
 #pragma unroll
         for (int j = 0; j < REI; j++) {
             const uint64_t b = p0 + j;
@@ -235,7 +200,7 @@ __global__ __launch_bounds__(RT) void runs_kernel(const uint32_t *__restrict__ w
                 u = upper_count(rs, ns, b);
                 owned = u != 0;
                 cur = b;
-                nxt = ent(u);
+                nxt = sv.ent(u);
             }
             if (!((m >> j) & 1u)) {
                 brk = b + 1;
@@ -261,7 +226,7 @@ __global__ __launch_bounds__(RT) void runs_kernel(const uint32_t *__restrict__ w
         const uint64_t r = r0 + (u - 1);
         if (r >= n_records) continue;  // (cannot happen: u <= ns and r0 + ns <= n_records)
         const uint64_t s = umin64(rs[u - 1], tb + i);
-        const uint64_t e = umin64(ent(u), n_bases);
+        const uint64_t e = umin64(sv.ent(u), n_bases);
         const uint64_t len = key >> 13;
         const uint32_t field = (uint32_t)(key & 8191u);
         const uint64_t start = field == BEFORE ? umax64(carry, s) : tb + ((uint64_t)RTILE - field);

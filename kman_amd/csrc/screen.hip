@@ -16,12 +16,11 @@
 //              the key itself marks the hit (a lower bound that ends inside
 //              the bucket has probed the row it ends on), so a bucket of n
 //              rows costs floor(log2 n) + 1 key reads, and a hit one count read.
-//   records    thread 0 cuts the slice of d_rec_seq that owns the tile's bases
-//              (two upper bounds).  A slice of <= SCAP entries is staged in
-//              LDS and the windows find their record there; a larger one (many
-//              empty or one-base records) is searched in global memory.  A
-//              thread walks its 16 consecutive windows and searches again only
-//              where a window start passes the next record's first base.
+//   records    thread 0 cuts the slice of d_rec_seq that owns the tile's bases;
+//              a slice of <= SCAP entries is staged in LDS, a larger one is
+//              searched in global memory; a thread walks its 16 consecutive
+//              windows by runs of one record (tile_records.h: cut_slice,
+//              stage_slice, owner_walk).
 //   reduction  runs of one record are added to LDS slots (windows, hits: u32;
 //              count sum: u64), then each nonzero (slot, plane) is one 64-bit
 //              atomicAdd to d_out.  LDS path: slot = record - first record of
@@ -32,11 +31,9 @@
 //              in STILE / SCAP rounds of SCAP offsets.  Integer adds commute:
 //              the result does not depend on the order of the atomics.
 //
-// Bounds, not values: lo <= hi <= nt are clamped after loading, every key and
-// count index is < nt, every record index is inside the slice, every slot is
-// < SCAP; keys 0 and 2^64 - 1 are ordinary keys.  An index that does not
-// belong to the table, or keys that are not ascending, give wrong counts but
-// no wild address and no unbounded loop.
+// Bounds, not values: tile_records.h for the records and slots, screen_lookup.h
+// for the table; here every record that addresses d_out is checked against
+// n_records.
 //
 // Algorithmic bytes per valid window: 1 B code, one 16 B index pair, at most
 // floor(log2 bucket) + 1 random 8 B key reads (each a 64 B sector or more from
@@ -44,6 +41,7 @@
 #include "common.h"
 #include "kmer.h"
 #include "screen_lookup.h"
+#include "tile_records.h"
 
 namespace {
 
@@ -58,21 +56,6 @@ inline uint32_t host_steps_of(uint64_t len) {
     uint32_t s = 0;
     for (; len; len >>= 1) s++;
     return s;
-}
-
-// the number of entries of rs[0, n) that are <= b
-KMAN_DEV uint64_t upper_count(const uint64_t *rs, uint64_t n, uint64_t b) {
-    uint64_t lo = 0, len = n;
-    for (int s = 0; s < 64 && len; s++) {
-        const uint64_t half = len >> 1;
-        if (rs[lo + half] <= b) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(256) void table_index_kernel(const uint64_t *__restrict__ tkeys, uint64_t nt,
@@ -112,19 +95,16 @@ __global__ __launch_bounds__(ST) void screen_kernel(const uint8_t *__restrict__ 
     if (threadIdx.x == 0) {
         // the records that own bases [tb, last]: from the owner of tb (or the
         // first record, when none starts at or before tb) to the owner of last
-        const uint64_t last = smin64(tb + STILE, n_bases) - 1;
-        const uint64_t u0 = upper_count(rec_seq, n_records, tb), u1 = upper_count(rec_seq, n_records, last);
-        const uint64_t r0 = u0 ? u0 - 1 : 0;
-        s_r0 = r0;
-        s_ns = u1 > r0 ? u1 - r0 : 0;
+        const TileSlice s = cut_slice(rec_seq, n_records, tb, umin64(tb + STILE, n_bases) - 1);
+        s_r0 = s.r0;
+        s_ns = s.ns;
     }
     stage_codes<ST, SEI>(codes, n_bases, tb, scodes);
     __syncthreads();
     const uint64_t r0 = s_r0, ns = s_ns;
     if (ns == 0) return;  // (no record starts at or before the tile's last base)
-    const bool big = ns > (uint64_t)SCAP;
-    if (!big)
-        for (uint32_t i = threadIdx.x; i < (uint32_t)ns; i += ST) srec[i] = rec_seq[r0 + i];
+    const SliceView sv = stage_slice<ST, SCAP>(rec_seq, {r0, ns, 0}, srec);
+    const bool big = sv.big;
 
     const uint64_t mask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
     uint64_t kf[SEI], kr[SEI];
@@ -136,7 +116,10 @@ __global__ __launch_bounds__(ST) void screen_kernel(const uint8_t *__restrict__ 
     const uint32_t hit = table_lookup<SEI, CT>(valid, kf, shift, index, tkeys, tcounts, nt, cnt);
 
     // ---- per-record reduction
-    const uint64_t *rs = big ? rec_seq + r0 : srec;
+    struct Run {
+        uint32_t h;
+        uint64_t sum;
+    };
     const int rounds = big ? STILE / SCAP : 1;
     for (int c = 0; c < rounds; c++) {
         for (uint32_t i = threadIdx.x; i < (uint32_t)SCAP; i += ST) {
@@ -145,45 +128,18 @@ __global__ __launch_bounds__(ST) void screen_kernel(const uint8_t *__restrict__ 
             ss[i] = 0;
         }
         __syncthreads();  // (and, in round 0, the slice in srec)
-        if (valid) {
-            const uint64_t slot0 = (uint64_t)c * SCAP;
-            uint64_t u = 0, nxt = 0;  // u: slice entries <= the current base; nxt: the base where that changes
-            uint32_t w = 0, h = 0;
-            uint64_t sum = 0;
-            auto flush = [&]() {
-                if (w == 0 || u == 0) return;  // (u == 0: bases before the first record)
-                const uint64_t ri = u - 1;
-                uint64_t key = ri;
-                if (big) {
-                    const uint64_t st = rs[ri];
-                    key = st > tb ? st - tb : 0;
-                }
-                if (key >= slot0 && key - slot0 < (uint64_t)SCAP) {
-                    const uint32_t slot = (uint32_t)(key - slot0);
+        if (valid)
+            owner_walk<SEI, SCAP, Run>(
+                sv, r0, tb, p0, valid, c, srec,
+                [&](Run &a, int j) {
+                    a.h += (hit >> j) & 1u;
+                    a.sum += cnt[j];
+                },
+                [&](const Run &a, uint32_t w, uint32_t slot) {
                     atomicAdd(&sw[slot], w);
-                    if (h) atomicAdd(&sh[slot], h);
-                    if (sum) atomicAdd(&ss[slot], (unsigned long long)sum);
-                    if (big) srec[slot] = r0 + ri;  // (every writer of a slot stores the same record)
-                }
-            };
-#pragma unroll
-            for (int j = 0; j < SEI; j++) {
-                const uint64_t b = p0 + j;
-                if (j == 0 || b >= nxt) {
-                    flush();
-                    w = h = 0;
-                    sum = 0;
-                    u = upper_count(rs, ns, b);
-                    nxt = u < ns ? rs[u] : ~0ull;
-                }
-                if ((valid >> j) & 1u) {
-                    w++;
-                    h += (hit >> j) & 1u;
-                    sum += cnt[j];
-                }
-            }
-            flush();
-        }
+                    if (a.h) atomicAdd(&sh[slot], a.h);
+                    if (a.sum) atomicAdd(&ss[slot], (unsigned long long)a.sum);
+                });
         __syncthreads();
         for (uint32_t i = threadIdx.x; i < (uint32_t)SCAP; i += ST) {
             const uint32_t wv = sw[i];

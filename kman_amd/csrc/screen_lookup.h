@@ -1,6 +1,8 @@
-// screen_lookup.h — the table lookup that screen.hip (kman_screen_records) and
-// quantile.hip (kman_window_counts) share: a thread's EI windows against a
-// key-sorted table through the prefix index of kman_table_index.
+// screen_lookup.h — the table lookup that the kernels over a count table share
+// (screen.hip, quantile.hip, classify.hip, correct.hip, unitig.hip): a thread's
+// EI windows against a key-sorted table through the prefix index of
+// kman_table_index.  table_rows is the search, table_lookup reads the count of
+// the row it ends on.
 //
 // The EI searches advance in lockstep: the EI index pairs are loaded, then
 // step 1 of all EI searches, then step 2, ..: EI independent loads in flight
@@ -19,8 +21,6 @@
 
 namespace {
 
-KMAN_DEV uint64_t smin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
 // halvings that empty a range of len rows: bits(len), 0 for an empty one
 KMAN_DEV uint32_t steps_of(uint64_t len) { return len ? 64u - (uint32_t)__builtin_clzll(len) : 0u; }
 
@@ -29,14 +29,15 @@ inline bool index_bits_ok(uint32_t k, uint32_t index_bits) {
     return index_bits >= 1 && index_bits <= top;
 }
 
-// The windows j with bit j of `valid` set are looked up by kf[j]; returns the
-// mask of those that are rows of the table, cnt[j] = the row's count (0 for
-// the others).
-template <int EI, typename CT>
-KMAN_DEV uint32_t table_lookup(uint32_t valid, const uint64_t (&kf)[EI], uint32_t shift,
-                               const uint64_t *__restrict__ index, const uint64_t *__restrict__ tkeys,
-                               const CT *__restrict__ tcounts, uint64_t nt, uint64_t (&cnt)[EI]) {
-    uint64_t lo[EI], len[EI];
+// The lockstep search.  The windows j with bit j of `valid` set are looked up
+// by kf[j]; returns the mask of those that are rows of the table, and row[j] =
+// where window j's lower bound ended: row[j] < nt for every bit of the mask.
+template <int EI>
+KMAN_DEV uint32_t table_rows(uint32_t valid, const uint64_t (&kf)[EI], uint32_t shift,
+                             const uint64_t *__restrict__ index, const uint64_t *__restrict__ tkeys, uint64_t nt,
+                             uint64_t (&row)[EI]) {
+    uint64_t (&lo)[EI] = row;
+    uint64_t len[EI];
 #pragma unroll
     for (int j = 0; j < EI; j++) {
         const bool ok = (valid >> j) & 1u;
@@ -47,8 +48,8 @@ KMAN_DEV uint32_t table_lookup(uint32_t valid, const uint64_t (&kf)[EI], uint32_
     uint32_t nsteps = 0;
 #pragma unroll
     for (int j = 0; j < EI; j++) {
-        const uint64_t hi = smin64(len[j], nt);  // lo <= hi <= nt whatever the index holds
-        lo[j] = smin64(lo[j], hi);
+        const uint64_t hi = umin64(len[j], nt);  // lo <= hi <= nt whatever the index holds
+        lo[j] = umin64(lo[j], hi);
         len[j] = hi - lo[j];
         const uint32_t s = steps_of(len[j]);
         nsteps = s > nsteps ? s : nsteps;
@@ -71,9 +72,22 @@ KMAN_DEV uint32_t table_lookup(uint32_t valid, const uint64_t (&kf)[EI], uint32_
             }
         }
     }
-    // a hit's row is where its lower bound ended (lo < nt then)
+    // a hit's row is where its lower bound ended (the search never passes the row it has probed: lo < nt then)
+    uint32_t ok = 0;
 #pragma unroll
-    for (int j = 0; j < EI; j++) cnt[j] = ((hit >> j) & 1u) && lo[j] < nt ? (uint64_t)tcounts[lo[j]] : 0;
+    for (int j = 0; j < EI; j++) ok |= (uint32_t)(((hit >> j) & 1u) && lo[j] < nt) << j;
+    return ok;
+}
+
+// table_rows with the hit row's count: cnt[j] = the row's count (0 for the others)
+template <int EI, typename CT>
+KMAN_DEV uint32_t table_lookup(uint32_t valid, const uint64_t (&kf)[EI], uint32_t shift,
+                               const uint64_t *__restrict__ index, const uint64_t *__restrict__ tkeys,
+                               const CT *__restrict__ tcounts, uint64_t nt, uint64_t (&cnt)[EI]) {
+    uint64_t row[EI];
+    const uint32_t hit = table_rows<EI>(valid, kf, shift, index, tkeys, nt, row);
+#pragma unroll
+    for (int j = 0; j < EI; j++) cnt[j] = (hit >> j) & 1u ? (uint64_t)tcounts[row[j]] : 0;
     return hit;
 }
 

@@ -6,9 +6,9 @@
 //   neighbours  the 4 keys that extend the row's k-mer to the right (side R)
 //               and the 4 that extend it to the left (side L) are folded to
 //               their canonical form and looked up through the prefix index of
-//               kman_table_index: the 8 searches advance in lockstep, as
-//               screen_lookup.h's table_lookup does, and a hit keeps the ROW
-//               its lower bound ended on.  A side with exactly one hit writes
+//               kman_table_index: the 8 searches advance in lockstep
+//               (screen_lookup.h's table_rows), and a hit keeps the ROW its
+//               lower bound ended on.  A side with exactly one hit writes
 //               (row << 1 | side entered) to a scratch word, every other side
 //               KMAN_GRAPH_NONE.
 //   mutual      side u keeps its word v when v's own word is u and v is a side
@@ -47,7 +47,7 @@
 //            its unitig's "-" end, a last row (pos >> 1 == nodes[start] - 1)
 //            (row, exit side) as the "+" end.
 //   edges    one thread per END, tiles of ETILE: the 4 extensions of the end's
-//            oriented k-mer are looked up in lockstep (row_lookup<4>), each hit
+//            oriented k-mer are looked up in lockstep (table_rows<4>), each hit
 //            (j, t) becomes (ord[start[j]] << 1) | p, "+" when j is a head
 //            entered at t; the up to 4 words and the end's offset (block scan,
 //            decoupled look-back) go to scratch.
@@ -89,55 +89,6 @@ KMAN_DEV uint64_t rc_key(uint64_t x, uint32_t k) {
     return __builtin_bswap64(x) >> (64 - 2 * k);
 }
 
-// table_lookup of screen_lookup.h with the hit's ROW for its count: the same
-// clamping (lo <= hi <= nt, every key index < nt), the same fixed step count.
-// row[j] < nt for every j of the returned mask.
-template <int EI>
-KMAN_DEV uint32_t row_lookup(const uint64_t (&kf)[EI], uint32_t shift, const uint64_t *__restrict__ index,
-                             const uint64_t *__restrict__ tkeys, uint64_t nt, uint64_t (&row)[EI]) {
-    uint64_t lo[EI], len[EI];
-#pragma unroll
-    for (int j = 0; j < EI; j++) {
-        const uint64_t p = kf[j] >> shift;  // (kf < 2^2k: p < 2^index_bits)
-        lo[j] = index[p];
-        len[j] = index[p + 1];
-    }
-    uint32_t nsteps = 0;
-#pragma unroll
-    for (int j = 0; j < EI; j++) {
-        const uint64_t hi = smin64(len[j], nt);  // lo <= hi <= nt whatever the index holds
-        lo[j] = smin64(lo[j], hi);
-        len[j] = hi - lo[j];
-        const uint32_t s = steps_of(len[j]);
-        nsteps = s > nsteps ? s : nsteps;
-    }
-    uint32_t hit = 0;
-    for (uint32_t s = 0; s < nsteps; s++) {  // (nsteps <= 64)
-        uint64_t v[EI];
-#pragma unroll
-        for (int j = 0; j < EI; j++) v[j] = len[j] ? tkeys[lo[j] + (len[j] >> 1)] : 0;  // (lo + half < lo + len <= nt)
-#pragma unroll
-        for (int j = 0; j < EI; j++) {
-            const uint64_t half = len[j] >> 1;
-            const bool on = len[j] != 0;
-            hit |= (uint32_t)(on && v[j] == kf[j]) << j;
-            if (on && v[j] < kf[j]) {
-                lo[j] += half + 1;
-                len[j] -= half + 1;
-            } else {
-                len[j] = half;
-            }
-        }
-    }
-    uint32_t ok = 0;  // a hit's row is where its lower bound ended
-#pragma unroll
-    for (int j = 0; j < EI; j++) {
-        row[j] = lo[j];
-        ok |= (uint32_t)(((hit >> j) & 1u) && lo[j] < nt) << j;
-    }
-    return ok;
-}
-
 // ---------------------------------------------------------------- links
 __global__ __launch_bounds__(UT) void neighbours_kernel(const uint64_t *__restrict__ tkeys, uint32_t nt, uint32_t k,
                                                         const uint64_t *__restrict__ index, uint32_t shift,
@@ -156,7 +107,7 @@ __global__ __launch_bounds__(UT) void neighbours_kernel(const uint64_t *__restri
         kf[j] = y < r ? y : r;
         fwd |= (uint32_t)(y < r) << j;
     }
-    const uint32_t hit = row_lookup<8>(kf, shift, index, tkeys, (uint64_t)nt, row);
+    const uint32_t hit = table_rows<8>(~0u, kf, shift, index, tkeys, (uint64_t)nt, row);
 #pragma unroll
     for (int s = 0; s < 2; s++) {
         const uint32_t h = (hit >> (4 * s)) & 15u;
@@ -400,7 +351,7 @@ __global__ __launch_bounds__(UT) void edges_kernel(const uint64_t *__restrict__ 
             kf[j] = y < r ? y : r;
             fwd |= (uint32_t)(y < r) << j;
         }
-        const uint32_t hit = row_lookup<4>(kf, shift, index, tkeys, (uint64_t)nt, row);
+        const uint32_t hit = table_rows<4>(~0u, kf, shift, index, tkeys, (uint64_t)nt, row);
         const uint64_t nu = n_ends >> 1;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -438,10 +389,10 @@ __global__ __launch_bounds__(UT) void edges_write_kernel(const uint4 *__restrict
     const uint64_t e = (uint64_t)blockIdx.x * UT + threadIdx.x;
     if (e >= n_ends) return;
     if (e == 0) d_eoff[n_ends] = total;
-    const uint64_t a = smin64(eoff[e], total);
-    const uint64_t b = smin64(e + 1 < n_ends ? eoff[e + 1] : total, total);
+    const uint64_t a = umin64(eoff[e], total);
+    const uint64_t b = umin64(e + 1 < n_ends ? eoff[e + 1] : total, total);
     d_eoff[e] = a;
-    const uint64_t c = b > a ? smin64(b - a, 4) : 0;  // (a + c <= b <= total)
+    const uint64_t c = b > a ? umin64(b - a, 4) : 0;  // (a + c <= b <= total)
     const uint4 w = ew[e];
     if (c > 0) d_edge[a] = w.x;
     if (c > 1) d_edge[a + 1] = w.y;

@@ -210,7 +210,7 @@ def test_header_signatures_and_documents():
         assert phrase in section, phrase
     with open(os.path.join(N.HERE, "csrc", "unitig.hip")) as fh:
         src = fh.read()
-    assert '"unitig_edges"' in src and "row_lookup<4>" in src and "layout_kernel<false>" in src
+    assert '"unitig_edges"' in src and "table_rows<4>" in src and "layout_kernel<false>" in src
     for doc in ("README.md", "DESIGN.md"):
         with open(os.path.join(root, doc)) as fh:
             body = fh.read()

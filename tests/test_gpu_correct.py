@@ -172,6 +172,31 @@ def test_more_records_in_a_tile_than_the_lds_slice(dev):
     assert sum(1 for f in want if f != NOFIX) == 3
 
 
+def _tile_of_tiny_records(entries):
+    """Tile 0 holds exactly T bases and `entries` records: three reads, then
+    one-base and empty records up to its last base; tile 1 is one read."""
+    g, lead = _genome(200, 2), _genome(T, 3)
+    tiny = ["", "A"] * ((entries - 3) // 2)
+    tiny = ["A"] * ((entries - 3) % 2) + tiny  # (ends with a one-base record: no empty one slips to base T)
+    fill = T - 300 - tiny.count("A")
+    recs = [("a", cc.sub(g[:150], 70)), ("lead", lead[:fill]), ("b", cc.sub(g[20:170], 0))]
+    recs += [("t%d" % i, s) for i, s in enumerate(tiny)] + [("c", cc.sub(g[50:], 149, 3))]
+    return recs, cc.kmer_table([g, lead], 15)
+
+
+@pytest.mark.parametrize("entries", [CAP, CAP + 1])
+def test_a_tile_with_exactly_the_lds_slice_and_one_more(dev, entries):
+    """The fullest tile's slice of d_rec_seq has exactly CAP entries (the
+    largest that is staged in LDS) and CAP + 1 (the smallest searched in
+    global memory)."""
+    recs, table = _tile_of_tiny_records(entries)
+    _, rec_seq, n = sc.codes_of(recs)
+    per_tile = np.bincount((rec_seq // T).astype(np.int64))
+    assert n == T + 150 and per_tile.tolist() == [entries, 1] and rec_seq[0] == 0 and rec_seq[-1] == T
+    want = _check(dev, recs, 15, table, 3)
+    assert sum(1 for f in want if f != NOFIX) == 3
+
+
 def test_one_long_record(dev):
     k, C = 21, 3
     g = _genome(10_000, 4)

@@ -190,7 +190,7 @@ def test_header_section_signatures_and_constants_agree():
         src = fh.read()
     for tag in ('"graph_links"', '"graph_rank"', '"unitig_spell"'):
         assert tag in src
-    assert "asm" not in src and "row_lookup" in src and '#include "screen_lookup.h"' in src
+    assert "asm" not in src and "table_rows<" in src and '#include "screen_lookup.h"' in src
 
 
 # -------------------------------------------------------------------- the CLI
